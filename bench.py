@@ -15,7 +15,11 @@ Launching.  `python bench.py --gpus N` works both ways:
     (127.0.0.1 rendezvous on a free port) and relays rank 0's JSON line.
 Weak scaling (bs=32 per GPU); value = images of all ranks / max-over-ranks time.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the JSON line (ms_per_step = timed region / steps).
+--dump-outputs DIR writes what the last timed step computed, as a caller of Segmentor.train_step receives it: the loss
+(loss.npy) and the updated network state (net.<state_dict key>.npy), float32 / float64, from rank 0.
+
+Extra objects on the JSON line, measured only with --full (each in runs of its own after the timed region):
   roofline      – the dominant kernel family (MFMA direct convolution: forward + dgrad launches), timed
                   with HIP events on the launch stream; algorithmic FLOPs = 2*Cin*Cout*k^2*H*W per conv
                   launch (UpsampleBlock 1x1 convs counted at the LOW resolution they are executed at,
@@ -26,6 +30,7 @@ Extra objects on the JSON line:
                   covariance) timed in the same process (N=1 only).
   cpu_baseline  – oracle/seg_oracle.py (the CPU restatement through stock PyTorch CPU ops) timed on the
                   host cores at the best thread count of a small sweep (rank 0, N=1 only).
+  per-rank diagnosis of a multi-GPU run (N>1 or AMX_BENCH_FORCE_DP=1): DESIGN.md section 4 "First 8-GPU run".
 """
 import argparse
 import glob
@@ -373,6 +378,27 @@ def _relay_stderr(ef, rank: int, n: int, tail=None) -> None:
     sys.stderr.flush()
 
 
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, net):
+    """What the last timed step handed its caller: the loss train_step returned and the network state it left behind
+    (weights after Adam, BatchNorm running statistics).  Two builds run with the same arguments can be compared file by
+    file: the inputs and the initial weights are seeded."""
+    arrays = {"loss": np.array([loss], dtype=np.float32)}
+    for k, v in net.state_dict().items():
+        a = v.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)                         # num_batches_tracked (int64)
+        arrays["net." + k] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > MAX_DUMP_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {MAX_DUMP_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def extra_configs():
     """Bounded samples of BASELINE.json configs[2..4], each timed by its own harness in tools/bench_extra.py."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -472,8 +498,13 @@ def main(argv=None, backend=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and network state of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: sustained, per-kernel roofline, multi-GPU diagnosis, "
+                         "configs[2..4], CPU baseline (the --no-* switches and --sustain-seconds apply to these)")
     ap.add_argument("--sustain-seconds", type=float, default=10.0,
-                    help="length of the steady-state leg after the timed region (0 = skip)")
+                    help="--full: length of the steady-state leg after the timed region (0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the configs[2..4] one-liners")
@@ -512,11 +543,12 @@ def main(argv=None, backend=None):
     model = aoi.models.Segmentor("Unet", nb_classes=3, seed=1, nb_filters=args.nb_filters)
     model.compile_trainer((X, y, X[:bs], y[:bs]), loss="ce", training_cycles=args.steps + args.warmup,
                           batch_size=bs, plot_training_history=False)
+    diagnose = (world > 1 or force_dp) and args.full
     if world > 1 or force_dp:
         model.dp = DataParallelGrads(model.optimizer, model.net)
-    if world > 1 or force_dp:
+    if diagnose:
         model.dp.timing = True                               # HIP events around the gradient all-reduce of every step
-    timer = None if (args.no_kernel_timing or not be.product) else KernelTimer(
+    timer = None if (not args.full or args.no_kernel_timing or not be.product) else KernelTimer(
         ["amx_conv2d_fwd", "amx_conv2d_dgrad", "amx_conv2d_dgrad_fused", "amx_conv2d_dgrad_fused_bsum", "amx_conv2d_wgrad",
          "amx_conv2d_wgrad_fused"])
     from atomai_amd.engine import Tape
@@ -558,10 +590,12 @@ def main(argv=None, backend=None):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:          # before any --full leg trains the network further
+        dump_outputs(args.dump_outputs, losses[-1], model.net)
 
     # ---- sustained leg: the same step for >= sustain-seconds (every rank runs the same, pre-agreed step count)
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         n_sus = max(args.steps, int(np.ceil(args.sustain_seconds / (elapsed / args.steps))))
         clk = ClockSampler(local)
         clk0 = clk.read()
@@ -593,7 +627,7 @@ def main(argv=None, backend=None):
     # ranks and steps), the host time it needs to ENQUEUE one step (eight launch threads share one host), its shader clock
     # under load, and whether the node reports xGMI links at all.  How to read it: DESIGN.md section 4 "First 8-GPU run".
     dp_info = None
-    if world > 1 or force_dp:
+    if diagnose:
         ar = model.dp.allreduce_ms()[args.warmup:args.warmup + args.steps]        # the timed region's collectives
         host_ms = host_enqueue_ms(model, nb, sync)
         clk_s = sorted(sustained["_sclk_own"]) if (sustained and sustained.get("_sclk_own")) else []
@@ -716,7 +750,7 @@ def main(argv=None, backend=None):
                                      "kernel": "wgrad_ws_kernel<NT,WM,WN,TH> (wave-specialised, <= 32 input channels) + wgrad_kernel<TAPS,NT,WM,HALO> "
                                                "(amx_conv2d_wgrad_fused: all weight-gradient launches of the step)",
                                      "ms_per_step": round(wg["total_ms"] / ksteps, 3)}
-    if world == 1 and be.product:
+    if world == 1 and be.product and args.full:
         del model
         torch.cuda.empty_cache()
         if not args.no_extra:

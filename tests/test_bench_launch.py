@@ -2,13 +2,15 @@
 emulator, tiny shape override):
   * `python bench.py --gpus 2` with NO launcher spawns its two ranks itself and prints ONE JSON line (n_gpus 2);
   * the same command under `python -m torch.distributed.run` (the driver's N>1 command) works too;
-  * the line carries the fields the driver's contract names."""
+  * the line carries the fields the driver's contract names;
+  * a plain run times --steps steps and nothing else; --dump-outputs is repeatable; --full adds the other legs."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -34,7 +36,7 @@ def _clean_env():
 def test_plain_command_self_launches_two_ranks():
     if torch.cuda.is_available():
         pytest.skip("CPU/gloo tier")
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + TINY, env=_clean_env(),
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full"] + TINY, env=_clean_env(),
                        capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -56,7 +58,7 @@ def test_plain_command_self_launches_eight_ranks():
     run will be read by — every rank's own step time and the time of its gradient all-reduces."""
     if torch.cuda.is_available():
         pytest.skip("CPU/gloo tier")
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "8"] + TINY, env=_clean_env(),
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--full"] + TINY, env=_clean_env(),
                        capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -75,6 +77,37 @@ def test_plain_command_self_launches_eight_ranks():
     assert out["allreduce_ms_percentiles"]["p50"] <= out["allreduce_ms_percentiles"]["max"]
     assert len(out["host_enqueue_ms_per_step_per_rank"]) == 8 and all(v > 0 for v in out["host_enqueue_ms_per_step_per_rank"])
     assert "xgmi_seen" in out and "sclk_mhz_per_rank_min_median_max" in out and out["per_rank_spread_rel"] >= 0
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_times_its_steps_and_dumps_repeatable_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line only; --dump-outputs writes the loss and network state of the
+    last timed step, float32 / float64, and a second run with the same arguments writes the same arrays."""
+    if torch.cuda.is_available():
+        pytest.skip("CPU/gloo tier")
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1"] + TINY + ["--steps", "3", "--dump-outputs", str(d)],
+                           env=_clean_env(), capture_output=True, text=True, timeout=500)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        out = lines[0]
+        for k in REQUIRED:
+            assert k in out
+        assert out["steps"] == 3 and len(out["step_ms_all"]) == 1 + 3
+        for k in ("sustained", "roofline", "per_rank_ms_per_step", "extra_configs", "cpu_baseline"):
+            assert k not in out
+        arrays = {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+        assert "loss" in arrays and any(k.startswith("net.") and k.endswith(".weight") for k in arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert abs(float(arrays["loss"][0]) - out["config"]["loss_first_last"][1]) < 1e-5
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 @pytest.mark.timeout(600)
