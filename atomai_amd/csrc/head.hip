@@ -327,7 +327,13 @@ extern "C" int amx_px_bwd(const float* dl, const float* a, const float* scale, c
 // lpart [rows]: per-workgroup loss sums (amx_reduce_rows with 1 / npix gives the mean, as for amx_ce_fwd_bwd).
 // BCE (KT == 1): the one-class head with BCEWithLogitsLoss against a float mask `tgtf` (select_loss('ce', 1), the
 // reference's default nb_classes): loss and gradient as bce_fwd_bwd_kernel forms them.
-template <int KT, bool BCE = false>
+// DICE: the same pass with the gradient of dice_loss (atomai/losses_metrics/losses.py:53-89; dice.hip) in place of the
+// cross-entropy one: `dtab` [B][2] = (a_j, b_j) of amx_dice_finalize, bins (class, column p % W) for K >= 2 and (foreground,
+// background) for K == 1 (target: the float mask, truncated as .long() does); no loss sums (lpart is not written).
+// LOSS == 2 (focal_loss, losses.py:13-50; KT == 1): the BCE form with the gradient times the device scalar dtab[0] = dF/dc
+// (amx_focal_from_bce of the mean BCE a first pass, amx_px_bce_sum, has formed).  The CE / BCE instantiations (LOSS == 0) do
+// not read the two extra arguments.
+template <int KT, bool BCE = false, int LOSS = 0>
 __global__ __launch_bounds__(256) void px_ce_train_kernel(const float* __restrict__ a, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, const float* __restrict__ w,
                                                           const float* __restrict__ b, const long long* __restrict__ tgt,
@@ -335,8 +341,10 @@ __global__ __launch_bounds__(256) void px_ce_train_kernel(const float* __restric
                                                           float* __restrict__ dxn, float* __restrict__ part,
                                                           float* __restrict__ partb, float* __restrict__ bstats,
                                                           float* __restrict__ lpart, long npix, int C, int Cs, int ppb,
-                                                          float inv_count) {
+                                                          float inv_count, const float* __restrict__ dtab, int W) {
     constexpr int K = KT;
+    constexpr bool DICE = LOSS == 1;
+    const float ic = LOSS == 2 ? inv_count * dtab[0] : inv_count;       // focal: d F / d logits = dF/dc * d c / d logits
     const int G = Cs >> 2, PL = 256 / G;                 // (256 % G == 0: every thread is active)
     const int tid = threadIdx.x;
     const int pl = tid / G, cg = tid - pl * G;
@@ -365,12 +373,20 @@ __global__ __launch_bounds__(256) void px_ce_train_kernel(const float* __restric
         int tv[U];
         float tf[U];
         bool ok[U];
+        float2 ab[DICE ? U : 1][DICE ? (KT == 1 ? 2 : KT) : 1];
         #pragma unroll
         for (int u = 0; u < U; ++u) {             // every load of the U pixels before the first use (see px_bwd_kernel)
             ok[u] = p + (long)u * PL < p1;
             const long pu = ok[u] ? p + (long)u * PL : p0;
             av[u] = amx_ld4(a + (size_t)pu * Cs + cg * 4);
             if (BCE) { tf[u] = tgtf[pu]; tv[u] = 0; } else { tv[u] = (int)tgt[pu]; tf[u] = 0.f; }
+            if (DICE) {
+                if (BCE) tv[u] = (int)(long long)tf[u];
+                const int wcol = KT == 1 ? 0 : (int)(pu % W);
+                #pragma unroll
+                for (int k = 0; k < (KT == 1 ? 2 : KT); ++k)
+                    ab[DICE ? u : 0][DICE ? k : 0] = *reinterpret_cast<const float2*>(dtab + 2 * ((size_t)k * (KT == 1 ? 1 : W) + wcol));
+            }
         }
         #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -388,10 +404,35 @@ __global__ __launch_bounds__(256) void px_ce_train_kernel(const float* __restric
                 lg[k] = t + bk[k];
             }
             float gk[KT], lterm;
-            if (BCE) {
+            if (DICE && BCE) {                    // dlogit = s (1 - s) (g_fg - g_bg)
+                const float xv = lg[0], e = expf(-fabsf(xv));
+                const float sg = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+                const float2 fg = ab[DICE ? u : 0][0], bg = ab[DICE ? u : 0][DICE ? 1 : 0];
+                lterm = 0.f;
+                gk[0] = sg * (1.f - sg) * ((tv[u] == 1 ? fg.x + fg.y : fg.y) - (tv[u] == 0 ? bg.x + bg.y : bg.y));
+            } else if (DICE) {                    // dlogit_k = p_k (g_k - sum_m p_m g_m)
+                float mx = lg[0];
+                #pragma unroll
+                for (int k = 1; k < KT; ++k) mx = fmaxf(mx, lg[k]);
+                float se = 0.f;
+                #pragma unroll
+                for (int k = 0; k < KT; ++k) { lg[k] = expf(lg[k] - mx); se += lg[k]; }
+                const float inv_s = 1.f / se;
+                float dot = 0.f;
+                #pragma unroll
+                for (int k = 0; k < KT; ++k) {
+                    const float2 t2 = ab[DICE ? u : 0][DICE ? k : 0];
+                    lg[k] *= inv_s;
+                    gk[k] = k == tv[u] ? t2.x + t2.y : t2.y;
+                    dot = fmaf(lg[k], gk[k], dot);
+                }
+                lterm = 0.f;
+                #pragma unroll
+                for (int k = 0; k < KT; ++k) gk[k] = lg[k] * (gk[k] - dot);
+            } else if (BCE) {
                 const float xv = lg[0], e = expf(-fabsf(xv));
                 lterm = fmaxf(xv, 0.f) - xv * tf[u] + log1pf(e);
-                gk[0] = ((xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e)) - tf[u]) * inv_count;
+                gk[0] = ((xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e)) - tf[u]) * ic;
             } else {
                 float mx = lg[0];
                 #pragma unroll
@@ -405,7 +446,7 @@ __global__ __launch_bounds__(256) void px_ce_train_kernel(const float* __restric
                 const float inv_s = 1.f / se;
                 lterm = logf(se) - xt;
                 #pragma unroll
-                for (int k = 0; k < KT; ++k) gk[k] = (lg[k] * inv_s - (k == tv[u] ? 1.f : 0.f)) * inv_count;
+                for (int k = 0; k < KT; ++k) gk[k] = (lg[k] * inv_s - (k == tv[u] ? 1.f : 0.f)) * ic;
             }
             if (!ok[u]) continue;
             if (cg == 0) lsum += lterm;
@@ -435,7 +476,7 @@ __global__ __launch_bounds__(256) void px_ce_train_kernel(const float* __restric
     amx_st4(sb + ((size_t)pl * Cs + cg * 4), bs1);
     amx_st4(sb + ((size_t)(PL + pl) * Cs + cg * 4), bs2);
     float* red = sb + (size_t)2 * PL * Cs;
-    red[tid] = lsum;
+    if (!DICE) red[tid] = lsum;
     __syncthreads();
     for (int i = tid; i < K * Cs; i += 256) {
         float acc = 0.f;
@@ -455,6 +496,7 @@ __global__ __launch_bounds__(256) void px_ce_train_kernel(const float* __restric
             bstats[((size_t)blockIdx.x * 2 + which) * Cs + c] = acc;
         }
     }
+    if (DICE) return;
     for (int o = 128; o > 0; o >>= 1) { __syncthreads(); if (tid < o) red[tid] += red[tid + o]; }
     if (tid == 0) lpart[blockIdx.x] = red[0];
 }
@@ -477,7 +519,8 @@ extern "C" int amx_px_ce_train(const float* a, const float* scale, const float* 
     const size_t lds = ((size_t)PL * K * Cs + (size_t)PL * K + 4 + (size_t)2 * PL * Cs + 256) * sizeof(float);
 #define PX_CE_LAUNCH(KT_)                                                                                             \
     AMX_LAUNCH((px_ce_train_kernel<KT_, KT_ == 1>), dim3(rows), dim3(256), lds, (hipStream_t)stream, a, scale, shift, w, b, \
-               target, target_f, dxn, part, partb, bstats, lpart, npix, C, Cs, rows_pix, 1.0f / (float)npix)
+               target, target_f, dxn, part, partb, bstats, lpart, npix, C, Cs, rows_pix, 1.0f / (float)npix,                  \
+               (const float*)nullptr, 1)
     switch (K) {
         case 1: PX_CE_LAUNCH(1); break;
         case 2: PX_CE_LAUNCH(2); break;
@@ -485,6 +528,52 @@ extern "C" int amx_px_ce_train(const float* a, const float* scale, const float* 
         default: PX_CE_LAUNCH(4); break;
     }
 #undef PX_CE_LAUNCH
+    AMX_CHECK_LAUNCH();
+    return 0;
+}
+
+// px forward + dice gradient + px backward (amx_px_dice_sums -> amx_reduce_rows_chunked -> amx_dice_finalize first: dice.hip)
+extern "C" int amx_px_dice_train_supported(int Cs, int K, int W);
+extern "C" int amx_px_dice_train(const float* a, const float* scale, const float* shift, const float* w, const float* b,
+                                 const long long* target, const float* target_f, const float* table, float* dxn,
+                                 float* part, float* partb, float* bstats, int N, int H, int W, int C, int Cs, int K,
+                                 int rows, int rows_pix, void* stream) {
+    if (!a || !w || !b || !table || !dxn || !part || !partb || C <= 0 || Cs < C) AMX_BADARG(1);
+    if (!amx_px_dice_train_supported(Cs, K, W) || (K == 1 ? !target_f : !target)) AMX_BADARG(2);
+    if ((scale == nullptr) != (shift == nullptr)) AMX_BADARG(3);
+    const long npix = (long)N * H * W;
+    if (rows <= 0 || rows_pix <= 0 || (long)rows * rows_pix < npix) AMX_BADARG(4);
+    const int PL = 256 / (Cs / 4);
+    const size_t lds = ((size_t)PL * K * Cs + (size_t)PL * K + 4 + (size_t)2 * PL * Cs + 256) * sizeof(float);
+#define PX_DICE_LAUNCH(KT_)                                                                                           \
+    AMX_LAUNCH((px_ce_train_kernel<KT_, KT_ == 1, 1>), dim3(rows), dim3(256), lds, (hipStream_t)stream, a, scale, shift, \
+               w, b, target, target_f, dxn, part, partb, bstats, (float*)nullptr, npix, C, Cs, rows_pix, 0.f, table, W)
+    switch (K) {
+        case 1: PX_DICE_LAUNCH(1); break;
+        case 2: PX_DICE_LAUNCH(2); break;
+        case 3: PX_DICE_LAUNCH(3); break;
+        default: PX_DICE_LAUNCH(4); break;
+    }
+#undef PX_DICE_LAUNCH
+    AMX_CHECK_LAUNCH();
+    return 0;
+}
+
+// px forward + focal gradient + px backward, one class: amx_px_ce_train (K = 1) with the logits gradient times *dfdc
+extern "C" int amx_px_focal_train(const float* a, const float* scale, const float* shift, const float* w, const float* b,
+                                  const float* target_f, const float* dfdc, float* dxn, float* part, float* partb,
+                                  float* bstats, float* lpart, int N, int H, int W, int C, int Cs, int rows, int rows_pix,
+                                  void* stream) {
+    if (!a || !w || !b || !target_f || !dfdc || !dxn || !part || !partb || !lpart || C <= 0 || Cs < C) AMX_BADARG(1);
+    if (!amx_px_ce_train_supported(Cs, 1)) AMX_BADARG(2);
+    if ((scale == nullptr) != (shift == nullptr)) AMX_BADARG(3);
+    const long npix = (long)N * H * W;
+    if (rows <= 0 || rows_pix <= 0 || (long)rows * rows_pix < npix) AMX_BADARG(4);
+    const int PL = 256 / (Cs / 4);
+    const size_t lds = ((size_t)PL * Cs + (size_t)PL + 4 + (size_t)2 * PL * Cs + 256) * sizeof(float);
+    AMX_LAUNCH((px_ce_train_kernel<1, true, 2>), dim3(rows), dim3(256), lds, (hipStream_t)stream, a, scale, shift, w, b,
+               (const long long*)nullptr, target_f, dxn, part, partb, bstats, lpart, npix, C, Cs, rows_pix,
+               1.0f / (float)npix, dfdc, 1);
     AMX_CHECK_LAUNCH();
     return 0;
 }

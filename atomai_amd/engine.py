@@ -1146,15 +1146,20 @@ class PxLossNode(_Node):
     """The training step's head in ONE pass (amx_px_ce_train): px -> CrossEntropyLoss (BCEWithLogitsLoss for one class) ->
     their backward, for the trainers'
     fused step (nets/fcnn.py: forward_loss).  value = the scalar mean loss; what px_bwd would have produced for an upstream
-    gradient of 1 is kept for backward, which only scales it if the upstream gradient is not 1."""
+    gradient of 1 is kept for backward, which only scales it if the upstream gradient is not 1.
+    kind 'dice' (criterion: losses.dice_loss): amx_px_dice_sums -> the coefficient table and the loss (amx_dice_finalize) ->
+    amx_px_dice_train, two passes over the last activation, the logits still never written.  kind 'focal' (losses.focal_loss,
+    one class), two passes as well: amx_px_bce_sum -> the mean BCE c -> value = F(c) and dF/dc (amx_focal_from_bce, device
+    scalars) -> amx_px_focal_train, the BCE form with dF/dc folded into the logits gradient (a pass over dxn would cost more)."""
 
-    def __init__(self, tape, src: Act, conv, target: torch.Tensor):
+    def __init__(self, tape, src: Act, conv, target: torch.Tensor, kind: str = "ce", criterion=None):
         self.src, self.conv = src, conv
         src.consumed_by(self)
         K = conv.weight.shape[0]
         assert conv.weight.shape[1] == src.C and conv.weight.shape[2:] == (1, 1)
         assert target.numel() == src.npix and target.dtype == (torch.float32 if K == 1 else torch.int64)
-        self.K = K
+        assert kind in ("ce", "dice", "focal") and (kind != "focal" or K == 1)
+        self.K, self.kind = K, kind
         s = src
         rows = L.load().amx_rows_for(s.npix)
         rows_pix = L.load().amx_rows_pix(s.npix)
@@ -1165,14 +1170,34 @@ class PxLossNode(_Node):
         self.bstats = None
         if need and s.wants_bstats(self, tape.training):
             self.bstats = _empty((rows, 2, s.Cs), s.t)
-        lpart = _empty((rows,), s.t)
         sp = _sp(s.t)
-        L.call("amx_px_ce_train", L.ptr(s.t), L.ptr(s.scale), L.ptr(s.shift), L.ptr(conv.weight.detach()),
-               L.ptr(conv.bias.detach()), L.ptr(target.contiguous() if K > 1 else None),
-               L.ptr(target.contiguous() if K == 1 else None), L.ptr(self.dxn), L.ptr(self.part), L.ptr(self.partb),
-               L.ptr(self.bstats), L.ptr(lpart), s.N, s.H, s.W, s.C, s.Cs, K, rows, rows_pix, sp)
-        self.value = torch.empty((), dtype=torch.float32, device=s.t.device)
-        L.call("amx_reduce_rows", L.ptr(lpart), rows, 1, 1, 1.0 / s.npix, L.ptr(self.value), sp)
+        head = (L.ptr(s.t), L.ptr(s.scale), L.ptr(s.shift), L.ptr(conv.weight.detach()), L.ptr(conv.bias.detach()),
+                L.ptr(target.contiguous() if K > 1 else None), L.ptr(target.contiguous() if K == 1 else None))
+        if kind == "dice":
+            from .losses_metrics import losses as _losses
+            B, drows, nch = _losses.dice_launch_plan(s.N, K, s.H, s.W)
+            dpart = _empty((drows, 2 * B), s.t)
+            L.call("amx_px_dice_sums", *head, L.ptr(dpart), drows, s.N, s.H, s.W, s.C, s.Cs, K, sp)
+            table, self.value = _losses.dice_table_and_loss(dpart, B, drows, nch, criterion.eps, sp)
+            L.call("amx_px_dice_train", *head, L.ptr(table), L.ptr(self.dxn), L.ptr(self.part), L.ptr(self.partb),
+                   L.ptr(self.bstats), s.N, s.H, s.W, s.C, s.Cs, K, rows, rows_pix, sp)
+        elif kind == "focal":
+            from .losses_metrics import losses as _losses
+            drows = L.load().amx_dice_rows(s.N, s.H, s.W, 1)
+            bpart = _empty((drows, 4), s.t)
+            L.call("amx_px_bce_sum", *head[:5], head[6], L.ptr(bpart), drows, s.N, s.H, s.W, s.C, s.Cs, sp)
+            c = _empty((1,), s.t)
+            L.call("amx_reduce_rows", L.ptr(bpart), drows, 4, 1, 1.0 / s.npix, L.ptr(c), sp)
+            self.value, dfdc = _losses.focal_scalars(c, criterion.alpha, criterion.gamma)
+            lpart = _empty((rows,), s.t)
+            L.call("amx_px_focal_train", *head[:5], head[6], L.ptr(dfdc), L.ptr(self.dxn), L.ptr(self.part),
+                   L.ptr(self.partb), L.ptr(self.bstats), L.ptr(lpart), s.N, s.H, s.W, s.C, s.Cs, rows, rows_pix, sp)
+        else:
+            lpart = _empty((rows,), s.t)
+            L.call("amx_px_ce_train", *head, L.ptr(self.dxn), L.ptr(self.part), L.ptr(self.partb),
+                   L.ptr(self.bstats), L.ptr(lpart), s.N, s.H, s.W, s.C, s.Cs, K, rows, rows_pix, sp)
+            self.value = torch.empty((), dtype=torch.float32, device=s.t.device)
+            L.call("amx_reduce_rows", L.ptr(lpart), rows, 1, 1, 1.0 / s.npix, L.ptr(self.value), sp)
         self.rows = rows
         self.grad_out: Optional[torch.Tensor] = None
 
@@ -1202,11 +1227,20 @@ class PxLossNode(_Node):
             tape.accumulate(s, dxn)
 
 
-def px_loss_fusable(src: Act, conv, target) -> bool:
+def px_loss_fusable(src: Act, conv, target, kind: str = "ce") -> bool:
+    """Does the fused head + loss node take this head?  `target`: int64 class map [N][H][W] (K >= 2) or float mask
+    [N][1][H][W] (K == 1) — for every kind; the callers (trainer.train_step, forward_loss) have checked the layout."""
     K = conv.weight.shape[0]
-    return (FUSE_PX_LOSS and isinstance(target, torch.Tensor) and target.numel() == src.npix
-            and target.dtype == (torch.float32 if K == 1 else torch.int64)
-            and bool(L.load().amx_px_ce_train_supported(src.Cs, K)))
+    if not (FUSE_PX_LOSS and isinstance(target, torch.Tensor) and target.numel() == src.npix
+            and target.dtype == (torch.float32 if K == 1 else torch.int64)):
+        return False
+    if kind != "ce" and target.ndim != (4 if K == 1 else 3):
+        return False
+    if kind == "dice":
+        return bool(L.load().amx_px_dice_train_supported(src.Cs, K, src.W))
+    if kind == "focal" and K != 1:
+        return False
+    return kind in ("ce", "focal") and bool(L.load().amx_px_ce_train_supported(src.Cs, K))
 
 
 FUSE_PX_LOSS = _os.environ.get("AMX_FUSE_PX_LOSS", "1") != "0"
@@ -1328,11 +1362,11 @@ class Tape:
     def output(self, src: Act) -> OutputNode:
         return self._push(OutputNode(self, src))
 
-    def px(self, src: Act, conv, mode: int = 0, loss_target=None):
-        """The net's final 1x1 convolution; with `loss_target` (the trainers' fused step, training mode) the mean
-        cross-entropy loss against it instead of the logits — one pass, see PxLossNode."""
+    def px(self, src: Act, conv, mode: int = 0, loss_target=None, loss_kind: str = "ce", criterion=None):
+        """The net's final 1x1 convolution; with `loss_target` (the trainers' fused step, training mode) the loss against it
+        (mean cross-entropy, or the dice / focal loss of `criterion`) instead of the logits — see PxLossNode."""
         if loss_target is not None:
-            return self._push(PxLossNode(self, src, conv, loss_target))
+            return self._push(PxLossNode(self, src, conv, loss_target, loss_kind, criterion))
         return self._push(PxNode(self, src, conv, mode))
 
     def conv_dsum(self, src: Act, conv, bn, slope: float, acts) -> Act:

@@ -37,26 +37,36 @@ class _HipNet(nn.Module):
     # head + loss + their backward in a single pass over the last activation (engine.PxLossNode)
     _loss_target = None
     _loss_fused = False
+    _loss_spec = ("ce", None)                      # (kind, criterion) — a tuple: a criterion must not register as a submodule
 
     def _px(self, tape, act, conv, px_mode: int):
         from ..engine import px_loss_fusable
         tgt = self._loss_target
-        if tgt is not None and tape.training and px_mode == 0 and px_loss_fusable(act, conv, tgt):
+        kind, criterion = self._loss_spec
+        if tgt is not None and tape.training and px_mode == 0 and px_loss_fusable(act, conv, tgt, kind):
             self._loss_fused = True
-            return tape.px(act, conv, 0, loss_target=tgt)
+            return tape.px(act, conv, 0, loss_target=tgt, loss_kind=kind, criterion=criterion)
         return tape.px(act, conv, px_mode)
 
-    def forward_loss(self, x: torch.Tensor, target: torch.Tensor):
+    def forward_loss(self, x: torch.Tensor, target: torch.Tensor, criterion=None):
         """('loss', mean cross-entropy of net(x) against the int64 class map `target` [N][H][W] — for a one-class net the mean
         BCE-with-logits against the float mask [N][1][H][W]) when the head and the loss run as the fused node, else
-        ('logits', net(x)) — the caller then applies its criterion as usual.  Training mode only."""
-        if not self.training or any(len(m._forward_hooks) or len(m._forward_pre_hooks) for m in self.children()):
+        ('logits', net(x)) — the caller then applies its criterion as usual.  Training mode only.
+        `criterion`: a losses.dice_loss / losses.focal_loss instance selects that loss (same target layouts) instead."""
+        from ..losses_metrics.losses import dice_loss, focal_loss
+        kind = "ce"
+        if criterion is not None:
+            kind = "dice" if type(criterion) is dice_loss else "focal" if type(criterion) is focal_loss else None
+        ok = isinstance(target, torch.Tensor) and x.ndim == 4 and (
+            tuple(target.shape) in ((x.shape[0],) + tuple(x.shape[2:]), (x.shape[0], 1) + tuple(x.shape[2:])))
+        if (kind is None or (kind != "ce" and not ok) or not self.training
+                or any(len(m._forward_hooks) or len(m._forward_pre_hooks) for m in self.children())):
             return "logits", self.forward(x)
-        self._loss_target, self._loss_fused = target, False
+        self._loss_target, self._loss_fused, self._loss_spec = target, False, (kind, criterion)
         try:
             out = run_tape(self._build, x, list(self.parameters()), True)
         finally:
-            self._loss_target = None
+            self._loss_target, self._loss_spec = None, ("ce", None)
         return ("loss" if self._loss_fused else "logits"), out
 
 

@@ -152,9 +152,16 @@ class BaseTrainer:
         ce = type(self.criterion) is losses_metrics.losses.CrossEntropyLoss and tar.dtype == torch.int64 and tar.ndim == 3
         bce = (type(self.criterion) is losses_metrics.losses.BCEWithLogitsLoss and tar.dtype == torch.float32
                and tar.ndim == 4 and tar.shape[1] == 1 and tar.shape[0] == feat.shape[0] and tar.shape[2:] == feat.shape[2:])
-        if FUSE_LOSS and not self.compute_accuracy and (ce or bce) and hasattr(self.net, "forward_loss"):
+        # dice_loss / focal_loss with the reference's target layouts (int64 class map for >= 2 classes, float mask [N][1][H][W]
+        # for one) take the same node with their own kernels; every other criterion / layout goes through criterion(net(x), y)
+        tcrit = type(self.criterion)
+        alt = (tcrit in (losses_metrics.losses.dice_loss, losses_metrics.losses.focal_loss) and feat.ndim == 4
+               and tar.shape[0] == feat.shape[0] and tar.shape[-2:] == feat.shape[2:]
+               and ((tar.dtype == torch.int64 and tar.ndim == 3 and tcrit is losses_metrics.losses.dice_loss)
+                    or (tar.dtype == torch.float32 and tar.ndim == 4 and tar.shape[1] == 1)))
+        if FUSE_LOSS and not self.compute_accuracy and (ce or bce or alt) and hasattr(self.net, "forward_loss"):
             # head + loss + their backward in one pass over the last activation (nets/fcnn.py: forward_loss); the same values
-            kind, out = self.net.forward_loss(feat, tar)
+            kind, out = self.net.forward_loss(feat, tar, **({"criterion": self.criterion} if alt else {}))
             loss = out if kind == "loss" else self.criterion(out, tar)
         else:
             prob = self.net(feat)

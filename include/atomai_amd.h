@@ -304,6 +304,52 @@ int amx_px_ce_train_supported(int Cs, int K);
 int amx_px_ce_train(const float* a, const float* scale, const float* shift, const float* w, const float* b,
                     const long long* target, const float* target_f, float* dxn, float* part, float* partb, float* bstats,
                     float* lpart, int N, int H, int W, int C, int Cs, int K, int rows, int rows_pix, void* stream);
+/* ---- dice_loss / focal_loss (atomai/losses_metrics/losses.py:13-89, selected at :148-151); csrc/dice.hip.
+ * Dice: probas = softmax over K (K == 1: (sigmoid, 1 - sigmoid) against (y, 1 - y), y = labels.long()); per BIN j
+ * I_j = sum probas * onehot, C_j = sum (probas + onehot), loss = 1 - mean_j 2 I_j / (C_j + eps).  The reference sums over
+ * dims = (0,) + range(2, labels.ndimension()) (losses.py:85): K == 1 (labels (N,1,H,W)) -> 2 bins (foreground, background);
+ * K >= 2 (labels (N,H,W)) -> only N and H are summed: B = K * W bins, one per (class, image column) -> W is an argument.
+ * amx_dice_bins = B; amx_dice_rows = rows of the partial tensor part [rows][2][B] (I, then C) of both sums kernels.
+ * amx_dice_sums: NCHW logits + target (int64 [N][H][W]; K == 1: int64 or a float mask [N][1][H][W], truncated) -> part.
+ * amx_dice_finalize: sums [nch][2][B] (part folded to nch chunk rows by amx_reduce_rows_chunked; the chunks are added in
+ * order, fp64) -> table [B][2] = (a_j, b_j) = (-2 / (B (C_j + eps)), 2 I_j / (B (C_j + eps)^2)) and the scalar loss.
+ * amx_dice_bwd: dlogits (NCHW) for an upstream gradient of 1: K >= 2: p_k (g_k - sum_m p_m g_m), g = a_j onehot + b_j;
+ * K == 1: s (1 - s) (g_fg - g_bg).  Deterministic: a bin's partial lives in one thread, no floating-point atomics. */
+int amx_dice_bins(int K, int W);
+int amx_dice_rows(int N, int H, int W, int K);
+int amx_dice_sums(const float* logits, const long long* target, const float* target_f, float* part, int rows, int N,
+                  int K, int H, int W, void* stream);
+int amx_dice_finalize(const float* sums, int nch, int B, float eps, float* table, float* loss, void* stream);
+int amx_dice_bwd(const float* logits, const long long* target, const float* target_f, const float* table,
+                 float* dlogits, int N, int K, int H, int W, void* stream);
+/* The dice loss of a training step fused with the head, the analogue of amx_px_ce_train (trainers/trainer.py:201-207 with
+ * criterion = dice_loss()): amx_px_dice_sums forms a pixel's logits in registers from the last activation [npix][Cs] and
+ * writes only the bin partials (part as amx_dice_sums); after amx_dice_finalize, amx_px_dice_train recomputes the logits,
+ * forms dlogits from the table in registers and emits what amx_px_bwd emits (dxn, part [rows][K][Cs], partb [rows][K],
+ * bstats [rows][2][Cs] or NULL; rows = amx_rows_for(npix), rows_pix = amx_rows_pix(npix)) for an upstream gradient of 1.
+ * amx_px_dice_train_supported: 1 <= K <= 4 and Cs / 4 a power of two (the table is read through L2: no bound on W). */
+int amx_px_dice_train_supported(int Cs, int K, int W);
+int amx_px_dice_sums(const float* a, const float* scale, const float* shift, const float* w, const float* b,
+                     const long long* target, const float* target_f, float* part, int rows, int N, int H, int W, int C,
+                     int Cs, int K, void* stream);
+int amx_px_dice_train(const float* a, const float* scale, const float* shift, const float* w, const float* b,
+                      const long long* target, const float* target_f, const float* table, float* dxn, float* part,
+                      float* partb, float* bstats, int N, int H, int W, int C, int Cs, int K, int rows, int rows_pix,
+                      void* stream);
+/* Focal: F = alpha (1 - pt)^gamma c with c = mean BCEWithLogits and pt = exp(-c) — a scalar function of the MEAN BCE
+ * (losses.py:45-50).  c and dc / dlogits come from amx_bce_fwd_bwd / amx_px_ce_train (K = 1); amx_focal_from_bce writes the
+ * two device scalars F and dF/dc = alpha ((1 - pt)^gamma + c gamma (1 - pt)^(gamma - 1) pt); amx_mul_scalars (out = a * b)
+ * forms dF/dc times the upstream gradient, the factor amx_scale_unless_one applies to dlogits.  No host synchronisation.
+ * Fused with the head (one class): amx_px_bce_sum (the BCE terms summed over the last activation: part [rows][4], column 0,
+ * rows = amx_dice_rows(N, H, W, 1)) -> amx_reduce_rows -> amx_focal_from_bce -> amx_px_focal_train = amx_px_ce_train (K = 1)
+ * with the logits gradient times *dfdc, so that no pass over dxn is needed afterwards. */
+int amx_focal_from_bce(const float* c, float alpha, float gamma, float* loss_out, float* dfdc_out, void* stream);
+int amx_mul_scalars(const float* a, const float* b, float* out, void* stream);
+int amx_px_bce_sum(const float* a, const float* scale, const float* shift, const float* w, const float* b,
+                   const float* target_f, float* part, int rows, int N, int H, int W, int C, int Cs, void* stream);
+int amx_px_focal_train(const float* a, const float* scale, const float* shift, const float* w, const float* b,
+                       const float* target_f, const float* dfdc, float* dxn, float* part, float* partb, float* bstats,
+                       float* lpart, int N, int H, int W, int C, int Cs, int rows, int rows_pix, void* stream);
 /* IoU of SegTrainer.accuracy_fn (trainers/trainer.py:727-737 -> losses_metrics/metrics.py:16-95): per-image K x K
  * confusion counts of (label, thresholded softmax / sigmoid class map) in one pass over the NCHW logits, replacing the
  * reference's host round trip (cv2.threshold per image + squeeze_channels + torch.bincount).  Exactly one of truth_i64

@@ -1,5 +1,5 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) — one JSON line each, written to gpurun_out/.
-   python tools/bench_extra.py rvae|predict|dkl
+   python tools/bench_extra.py rvae|predict|dkl|losses
 """
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -434,11 +434,80 @@ def bench_locate(frames=32, hw=1024, C=1, emit=True):
     return out
 
 
+def bench_losses(hw=512, bs=32, steps=10, warmup=4, reps=3, emit=True):
+    """select_loss('dice' | 'focal') against the 'ce' step at the headline shape (U-Net, bs x hw x hw, fp32), interleaved in
+    one process: variants ce3 (nb_classes 3, the yardstick), dice3 (fused head + dice), dice3_general (AMX_FUSE_PX_LOSS=0
+    for that step: px -> dice kernels on logits -> px backward), bce1 / focal1 / dice1 (nb_classes 1).  `reps` rounds of
+    `steps` steps per variant, median of the rounds; then one event-timed step per variant for the head / loss launches
+    (their times and the bandwidth of the passes over the last activation, npix * Cs * 4 bytes read each)."""
+    import atomai_amd.engine as eng
+    import atomai_amd.trainers.trainer as tr
+    rs = np.random.RandomState(0)
+    X = rs.rand(bs, hw, hw).astype(np.float32)
+    y3 = rs.randint(0, 3, (bs, hw, hw))
+    y1 = (rs.rand(bs, hw, hw) < 0.03).astype(np.float32)             # a few percent of the pixels are atoms
+    variants = [("ce3", 3, "ce", True), ("dice3", 3, "dice", True), ("dice3_general", 3, "dice", False),
+                ("bce1", 1, "ce", True), ("focal1", 1, "focal", True), ("dice1", 1, "dice", True)]
+    models = {}
+    for name, ncls, loss, fused in variants:
+        m = aoi.models.Segmentor(nb_classes=ncls, seed=1)
+        yy = y3 if ncls == 3 else y1
+        m.compile_trainer((X, yy, X, yy), loss=loss, training_cycles=1, batch_size=bs, plot_training_history=False)
+        models[name] = m
+
+    def step(name, fused):
+        m = models[name]
+        tr.FUSE_LOSS = eng.FUSE_PX_LOSS = fused
+        try:
+            return m.train_step(m.X_train[0], m.y_train[0])[0]
+        finally:
+            tr.FUSE_LOSS = eng.FUSE_PX_LOSS = True
+    for name, _, _, fused in variants:
+        for _ in range(warmup):
+            step(name, fused)
+    times = {name: [] for name, *_ in variants}
+    for _ in range(reps):
+        for name, _, _, fused in variants:
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(steps):
+                last = step(name, fused)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / steps * 1e3)
+    names = {"amx_px_ce_train", "amx_px_dice_sums", "amx_px_dice_train", "amx_dice_finalize", "amx_reduce_rows_chunked",
+             "amx_px_bce_sum", "amx_px_focal_train",
+             "amx_px_fwd", "amx_px_bwd", "amx_dice_sums", "amx_dice_bwd", "amx_focal_from_bce", "amx_mul_scalars",
+             "amx_scale_unless_one_multi", "amx_ce_fwd_bwd", "amx_bce_fwd_bwd"}
+    recs = timed_calls(names)
+    import atomai_amd.losses_metrics.losses as lm
+    lm.L.call = L.call
+    act_bytes = bs * hw * hw * 16 * 4
+    res = {}
+    for name, ncls, loss, fused in variants:
+        recs.clear()
+        step(name, fused)
+        torch.cuda.synchronize()
+        launches = {}
+        for n, e0, e1 in recs:
+            launches[n] = round(launches.get(n, 0.0) + e0.elapsed_time(e1), 4)
+        r = {"ms_per_step": round(float(np.median(times[name])), 3), "rounds_ms": [round(t, 3) for t in times[name]],
+             "images_per_s": round(bs / float(np.median(times[name])) * 1e3, 1), "loss_path_launches_ms": launches}
+        for k in ("amx_px_ce_train", "amx_px_dice_sums", "amx_px_dice_train", "amx_px_bce_sum", "amx_px_focal_train"):
+            if k in launches:                       # train kernels also write dxn (as many bytes again)
+                r[k + "_GBps"] = round(act_bytes * (1 if k.endswith("sum") or k.endswith("sums") else 2) / launches[k] / 1e6, 1)
+        res[name] = r
+    out = {"metric": f"dice / focal training steps vs the 'ce' step, U-Net {hw}x{hw}, bs={bs}", "unit": "ms",
+           "value": res["dice3"]["ms_per_step"], "higher_is_better": False,
+           "last_activation_MB": round(act_bytes / 1e6, 1), "detail": res}
+    if emit:
+        print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["rvae", "predict"]
     os.makedirs("gpurun_out", exist_ok=True)
     res = {}
     for w in what:
-        res[w] = {"rvae": bench_rvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "segfamily": bench_segfamily,
+        res[w] = {"rvae": bench_rvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "segfamily": bench_segfamily, "losses": bench_losses,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)

@@ -1,5 +1,6 @@
 """Which ATen operators (copies, fills, elementwise) still run inside one U-Net training step, and from where:
-torch.profiler over 3 steady steps, CUDA-time per op name with the innermost atomai_amd / bench frame of its stack (dev tool)."""
+torch.profiler over 3 steady steps, CUDA-time per op name with the innermost atomai_amd / bench frame of its stack (dev tool).
+   python tools/gpu_aten_ops.py [loss (ce | dice | focal)] [nb_classes]"""
 import os, sys, collections
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -7,9 +8,12 @@ import atomai_amd as aoi
 from torch.profiler import profile, ProfilerActivity
 
 rs = np.random.RandomState(0)
-X = rs.rand(64, 512, 512).astype(np.float32); y = rs.randint(0, 3, (64, 512, 512))
-m = aoi.models.Segmentor("Unet", nb_classes=3, seed=1)
-m.compile_trainer((X, y, X[:32], y[:32]), training_cycles=10, batch_size=32)
+LOSS = sys.argv[1] if len(sys.argv) > 1 else "ce"
+NCLS = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+X = rs.rand(64, 512, 512).astype(np.float32)
+y = rs.randint(0, NCLS, (64, 512, 512)) if NCLS > 1 else (rs.rand(64, 512, 512) < 0.03).astype(np.float32)
+m = aoi.models.Segmentor("Unet", nb_classes=NCLS, seed=1)
+m.compile_trainer((X, y, X[:32], y[:32]), loss=LOSS, training_cycles=10, batch_size=32)
 for i in range(4): m.train_step(m.X_train[i % 2], m.y_train[i % 2])
 torch.cuda.synchronize()
 with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], with_stack=True) as prof:
