@@ -5,8 +5,9 @@ plain KL term together with the content latents).  The three per-sample terms â€
 KL(rotation) â€” come from ONE kernel (csrc/elbo.hip, forward and backward); only their means and the optional
 capacity term are combined here, on B-element vectors.
 """
-from typing import List, Tuple, Union
+from typing import List, Optional, Tuple, Union
 
+import numpy as np
 import torch
 
 from .. import _lib as L
@@ -89,11 +90,29 @@ def elbo_terms(x, x_rec, z_mean, z_logsd, rot: bool, phi_prior: float = 0.1, kin
     return _ElboTermsFn.apply(x, x_rec, z_mean, z_logsd, rot, phi_prior, kind, rscale)
 
 
-def infocapacity(kl_cont_loss: torch.Tensor, cont_capacity: List[float], num_iter: int = 0) -> torch.Tensor:
-    """gamma * |KL - C(num_iter)| (vi_losses.py:224-236, continuous channel)."""
+def infocapacity(kl_cont_loss: torch.Tensor, cont_capacity: List[float], kl_disc_loss: Optional[torch.Tensor] = None,
+                 disc_capacity: Optional[List[float]] = None, disc_dims: Optional[List[int]] = None,
+                 num_iter: int = 0) -> Union[torch.Tensor, Tuple[torch.Tensor]]:
+    """gamma * |KL - C(num_iter)| of the continuous channel and, when ``kl_disc_loss`` is given, of the discrete one
+    too, whose capacity is also capped by its theoretical maximum sum(log K_h) (vi_losses.py:224-251).  Device scalars
+    in, device scalars out: the capacities are host arithmetic on num_iter."""
     cont_max, cont_num_iters, cont_gamma = cont_capacity
     cont_cap = min(cont_max * (num_iter / float(cont_num_iters)), cont_max)
-    return cont_gamma * torch.abs(kl_cont_loss - cont_cap)
+    cont_capacity_loss = cont_gamma * torch.abs(kl_cont_loss - cont_cap)
+    if kl_disc_loss is None:
+        return cont_capacity_loss
+    disc_max, disc_num_iters, disc_gamma = disc_capacity
+    disc_theory_max = sum([float(np.log(d)) for d in disc_dims])
+    disc_cap = min(disc_max * (num_iter / float(disc_num_iters)), disc_max, disc_theory_max)
+    disc_capacity_loss = disc_gamma * torch.abs(disc_cap - kl_disc_loss)
+    return cont_capacity_loss, disc_capacity_loss
+
+
+def kld_discrete(alpha: torch.Tensor) -> torch.Tensor:
+    """Batch mean, shape (1,), of the KL divergence between the Gumbel-Softmax distribution with parameters ``alpha``
+    (B, K) and the uniform categorical (vi_losses.py:60-74); the per-sample sums come from csrc/joint.hip."""
+    from .._joint import kl_discrete_rows
+    return kl_discrete_rows(alpha).mean().view(1)
 
 
 def _check(recon_loss, args):
@@ -128,3 +147,39 @@ def rvae_loss(recon_loss: str, in_dim: Tuple[int], x: torch.Tensor, x_reconstr: 
     if kwargs.get("capacity") is not None:
         kl_div = infocapacity(kl_div, kwargs["capacity"], num_iter=kwargs.get("num_iter", 0))
     return -recon.mean() - kl_div
+
+
+def _joint_elbo(recon_loss: str, in_dim, x, x_reconstr, z_mean, z_logsd, kl_disc_loss: torch.Tensor, disc_dims: List[int],
+                rot: bool, kwargs) -> torch.Tensor:
+    """likelihood - cont_capacity_loss - disc_capacity_loss from the per-sample ELBO terms and the (scalar) discrete KL."""
+    kind, rscale = _recon_kind(recon_loss, in_dim)
+    recon, klz, klrot = elbo_terms(x, x_reconstr, z_mean, z_logsd, rot, kwargs.get("phi_prior", 0.1), kind, rscale)
+    kl_cont_loss = klz.mean() + klrot.mean() if rot else klz.mean()
+    cont_loss, disc_loss = infocapacity(kl_cont_loss, kwargs.get("cont_capacity", [5.0, 25000, 30]), kl_disc_loss,
+                                        kwargs.get("disc_capacity", [5.0, 25000, 30]), disc_dims,
+                                        kwargs.get("num_iter", 0))
+    return -recon.mean() - cont_loss - disc_loss
+
+
+def _check_joint(args):
+    if len(args) != 3:
+        raise ValueError("Pass continuous (mean, SD) and discrete (alphas) values of encoded distributions as args")
+    return args
+
+
+def joint_vae_loss(recon_loss: str, in_dim: Tuple[int], x: torch.Tensor, x_reconstr: torch.Tensor,
+                   *args: torch.Tensor, **kwargs: Union[List, int]) -> torch.Tensor:
+    """Joint ELBO for continuous and discrete latent variables (vi_losses.py:140-176)."""
+    z_mean, z_logsd, alphas = _check_joint(args)
+    kl_disc_loss = torch.sum(torch.cat([kld_discrete(alpha) for alpha in alphas]))
+    return _joint_elbo(recon_loss, in_dim, x, x_reconstr, z_mean, z_logsd, kl_disc_loss,
+                       [a.size(1) for a in alphas], False, kwargs)
+
+
+def joint_rvae_loss(recon_loss: str, in_dim: Tuple[int], x: torch.Tensor, x_reconstr: torch.Tensor,
+                    *args: torch.Tensor, **kwargs: Union[List, float, int]) -> torch.Tensor:
+    """Joint ELBO of the rotationally invariant model: the rotation latent gets kld_rot (vi_losses.py:179-221)."""
+    z_mean, z_logsd, alphas = _check_joint(args)
+    kl_disc_loss = torch.sum(torch.cat([kld_discrete(alpha) for alpha in alphas]))
+    return _joint_elbo(recon_loss, in_dim, x, x_reconstr, z_mean, z_logsd, kl_disc_loss,
+                       [a.size(1) for a in alphas], True, kwargs)

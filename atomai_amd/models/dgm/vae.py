@@ -27,6 +27,8 @@ class BaseVAE(viBaseTrainer):
         set_train_rng(seed)              # NB: the nets are always drawn under BaseVAE's own seed (default 0)
         self.in_dim = in_dim
         self.z_dim = latent_dim
+        if isinstance(discrete_dim, list):                   # joint models: vae.py:84-85
+            self.z_dim = self.z_dim + sum(discrete_dim)
         self.discrete_dim = discrete_dim
         if coord:
             if len(in_dim) not in (2, 3):
@@ -58,8 +60,13 @@ class BaseVAE(viBaseTrainer):
         return np.concatenate(out)
 
     def encode(self, x_new, **kwargs) -> Tuple[np.ndarray]:
+        """(z_mean, z_logsd), and for the joint models (z_mean, z_logsd, alphas) with the heads' probabilities side by
+        side (vae.py:145-176)."""
         z = self.encode_(x_new, **kwargs)
-        return z[:, :self.z_dim], z[:, self.z_dim:]
+        if not self.discrete_dim:
+            return z[:, :self.z_dim], z[:, self.z_dim:]
+        cont_dim = self.z_dim - sum(self.discrete_dim)
+        return z[:, :cont_dim], z[:, cont_dim:2 * cont_dim], z[:, 2 * cont_dim:]
 
     def decode(self, z_sample, y=None) -> np.ndarray:
         """Maps latent point(s) to data space with the trained generative model (vae.py:178-221)."""
@@ -90,6 +97,8 @@ class BaseVAE(viBaseTrainer):
     def reconstruct(self, x_new, **kwargs) -> np.ndarray:
         """Decodes ``num_samples`` draws from the encoded distribution of ONE input (vae.py:223-271; regular VAE:
         the coordinate latents are dropped)."""
+        if self.discrete_dim:
+            raise NotImplementedError("reconstruct() is not available for the joint models (jVAE / jrVAE)")
         num_samples = kwargs.get("num_samples", 32)
         label = kwargs.get("label")
         z_mean, z_sd = self.encode(x_new)

@@ -6,7 +6,7 @@ atomai/trainers/trainer.py:344-358 and atomai/trainers/vitrainer.py:361-377 in t
 written by the reference loads here onto the HIP modules (same state-dict keys / shapes), and files written
 here hold only torch types (the fused optimizer is stored as its ``torch.optim.Adam`` equivalent).
 
-Model families outside SURVEY.md section 8 (imspec / reg / cls / denoising autoencoder / joint VAEs) raise.
+Model families outside SURVEY.md section 8 (imspec / reg / cls / denoising autoencoder) raise.
 """
 import warnings
 from copy import deepcopy as dc
@@ -15,7 +15,7 @@ from typing import Dict, Tuple, Type, Union
 import torch
 
 from ..utils import average_weights
-from .dgm import VAE, BaseVAE, rVAE
+from .dgm import VAE, BaseVAE, jrVAE, jVAE, rVAE
 from .segmentor import Segmentor
 
 _OUT_OF_SCOPE = ("imspec", "reg", "cls", "denoising_autoencoder")
@@ -59,18 +59,19 @@ def load_seg_model(meta_dict: Dict) -> Type[Segmentor]:
 
 
 def load_vae_model(meta_dict: Dict) -> Type[BaseVAE]:
-    """VAE / rVAE from {in_dim, latent_dim, coord, encoder, decoder, optimizer, **kwargs}."""
+    """VAE / rVAE / jVAE / jrVAE from {in_dim, latent_dim, coord, encoder, decoder, optimizer, **kwargs}."""
     in_dim = meta_dict.pop("in_dim")
     latent_dim = meta_dict.pop("latent_dim")
     enc_w, dec_w = meta_dict.pop("encoder"), meta_dict.pop("decoder")
     coord = meta_dict.pop("coord")
     optimizer = meta_dict.pop("optimizer")
-    if meta_dict.get("discrete_dim"):
-        raise NotImplementedError("joint (discrete) VAEs are outside the MI355X hot path of this build")
+    joint = bool(meta_dict.get("discrete_dim"))
     if coord:
-        m = rVAE(in_dim, latent_dim, translation=(coord == 3), **meta_dict)
+        m = (jrVAE if joint else rVAE)(in_dim, latent_dim, translation=(coord == 3), **meta_dict)
     else:
-        m = VAE(in_dim, latent_dim, **meta_dict)
+        m = (jVAE if joint else VAE)(in_dim, latent_dim, **meta_dict)
+    if joint:                                                # the capacity schedule resumes where training stopped
+        m.kdict_["num_iter"] = meta_dict.get("num_iter", 0)
     m.encoder_net.load_state_dict(enc_w)
     m.encoder_net.eval()
     m.decoder_net.load_state_dict(dec_w)

@@ -306,6 +306,86 @@ class convEncoderNet(nn.Module):
                 self._out(linear(feats, self.fc12.weight, self.fc12.bias)))
 
 
+def _check_heads(discrete_dim) -> List[int]:
+    from .._joint import check_discrete_dim
+    return check_discrete_dim(discrete_dim)
+
+
+def _joint_heads(net, feats: torch.Tensor):
+    """(fc11, fc12, fc13[*]) of a joint encoder over the trunk's features: every head is one launch of the MFMA GEMM,
+    the softmax of ALL discrete heads one launch of the segmented row softmax (csrc/joint.hip).  Returns
+    (z_mean, z_logsd, alpha) with the heads' probabilities packed side by side in ``alpha`` (B, sum(discrete_dim))."""
+    from .._joint import seg_softmax
+    z_mean = linear(feats, net.fc11.weight, net.fc11.bias)
+    z_logsd = net._out(linear(feats, net.fc12.weight, net.fc12.bias))
+    logits = [linear(feats, fc.weight, fc.bias) for fc in net.fc13]
+    logits = logits[0] if len(logits) == 1 else torch.cat(logits, 1)
+    return z_mean, z_logsd, seg_softmax(logits, net.discrete_dim)
+
+
+def _split_heads(packed, sizes):
+    z_mean, z_logsd, alpha = packed
+    return [z_mean, z_logsd] + ([alpha] if len(sizes) == 1 else list(alpha.split(sizes, 1)))
+
+
+class jfcEncoderNet(nn.Module):
+    """fcEncoderNet with one softmax head per discrete latent variable: flatten -> [Linear -> Tanh] x num_layers ->
+    (fc11, fc12, fc13[0..H-1]) (ed.py:346-403).  ``forward`` returns [z_mean, z_logsd, alpha_0, ...]."""
+
+    def __init__(self, in_dim: Tuple[int], latent_dim: int = 2, discrete_dim: List = [1], num_layers: int = 2,
+                 hidden_dim: int = 32, **kwargs: bool) -> None:
+        super().__init__()
+        self.discrete_dim = _check_heads(discrete_dim)
+        if len(in_dim) == 1:
+            raise NotImplementedError("1-D (spectral) encoders are outside the MI355X hot path")
+        dense = []
+        for i in range(num_layers):
+            input_dim = int(np.prod(in_dim)) if i == 0 else hidden_dim
+            dense.extend([nn.Linear(input_dim, hidden_dim), nn.Tanh()])
+        self.dense = nn.Sequential(*dense)
+        self.reshape_ = hidden_dim
+        self.fc11 = nn.Linear(self.reshape_, latent_dim)
+        self.fc12 = nn.Linear(self.reshape_, latent_dim)
+        self.fc13 = nn.ModuleList([nn.Linear(self.reshape_, disc) for disc in self.discrete_dim])
+        self._out = nn.Softplus() if kwargs.get("softplus_out") else lambda x: x
+
+    def forward_packed(self, x: torch.Tensor):
+        x = x.reshape(-1, int(np.prod(x.size()[1:])))
+        return _joint_heads(self, run_dense(self.dense, x).reshape(-1, self.reshape_))
+
+    def forward(self, x: torch.Tensor):
+        return _split_heads(self.forward_packed(x), self.discrete_dim)
+
+
+class jconvEncoderNet(nn.Module):
+    """convEncoderNet with one softmax head per discrete latent variable (ed.py:406-468)."""
+
+    def __init__(self, in_dim: Tuple[int], latent_dim: int = 2, discrete_dim: List = [1], num_layers: int = 2,
+                 hidden_dim: int = 32, **kwargs) -> None:
+        super().__init__()
+        if len(in_dim) not in (1, 2, 3):
+            raise ValueError("The input dimensions must be (length,) for 1D data and "
+                             "(height, width) or (height, width, channel) for 2D data")
+        if len(in_dim) == 1:
+            raise NotImplementedError("1-D (spectral) encoders are outside the MI355X hot path")
+        self.discrete_dim = _check_heads(discrete_dim)
+        from .blocks import ConvBlock
+        channels = in_dim[-1] if len(in_dim) > 2 else 1
+        self.conv = ConvBlock(2, num_layers, channels, hidden_dim, lrelu_a=kwargs.get("lrelu_a", 0.1))
+        self.reshape_ = int(hidden_dim * np.prod(in_dim[:2]))
+        self.fc11 = nn.Linear(self.reshape_, latent_dim)
+        self.fc12 = nn.Linear(self.reshape_, latent_dim)
+        self.fc13 = nn.ModuleList([nn.Linear(self.reshape_, disc) for disc in self.discrete_dim])
+        self._out = nn.Softplus() if kwargs.get("softplus_out") else (lambda t: t)
+
+    def forward_packed(self, x: torch.Tensor):
+        x = x.unsqueeze(1) if x.ndim in (2, 3) else x.permute(0, -1, 1, 2)
+        return _joint_heads(self, self.conv(x.contiguous()).reshape(-1, self.reshape_))
+
+    def forward(self, x: torch.Tensor):
+        return _split_heads(self.forward_packed(x), self.discrete_dim)
+
+
 class convDecoderNet(nn.Module):
     """Convolutional decoder of the plain VAE (reference: atomai/nets/ed.py:471-527): bias-free Linear(latent ->
     hidden*H*W) on the MFMA GEMM -> reshape (B, hidden, H, W) -> ConvBlock(num_layers x [3x3 conv -> LeakyReLU(0.1)])
@@ -352,15 +432,21 @@ def init_VAE_nets(in_dim: Tuple[int], latent_dim: int, coord: int = 0, discrete_
     skip = kwargs.get("skip", False)
     sigmoid_out = kwargs.get("sigmoid_out", False)
     softplus_out = kwargs.get("softplus_out")
-    if discrete_dim:
-        raise NotImplementedError("joint (discrete) VAEs are outside the MI355X hot path of this build")
+    # joint models: the Gumbel-Softmax samples are further decoder latents and replace the class one-hot (ed.py:746-759)
+    discrete_dim_ = sum(_check_heads(discrete_dim)) if discrete_dim else 0
+    nb_classes_ = nb_classes if discrete_dim_ == 0 else 0
     if not coord:
         dnet = convDecoderNet if conv_d else fcDecoderNet
-        decoder_net = dnet(in_dim, latent_dim + nb_classes, numlayers_d, numhidden_d)
+        decoder_net = dnet(in_dim, latent_dim + discrete_dim_ + nb_classes_, numlayers_d, numhidden_d)
     else:
-        decoder_net = rDecoderNet(in_dim, latent_dim + nb_classes, numlayers_d, numhidden_d, skip)
-    enc_cls = convEncoderNet if conv_e else fcEncoderNet
-    encoder_net = enc_cls(in_dim, latent_dim + coord, numlayers_e, numhidden_e, softplus_out=softplus_out)
+        decoder_net = rDecoderNet(in_dim, latent_dim + discrete_dim_ + nb_classes_, numlayers_d, numhidden_d, skip)
+    if not discrete_dim:
+        enc_cls = convEncoderNet if conv_e else fcEncoderNet
+        encoder_net = enc_cls(in_dim, latent_dim + coord, numlayers_e, numhidden_e, softplus_out=softplus_out)
+    else:
+        enc_cls = jconvEncoderNet if conv_e else jfcEncoderNet
+        encoder_net = enc_cls(in_dim, latent_dim + coord, discrete_dim, numlayers_e, numhidden_e,
+                              softplus_out=softplus_out)
     meta_state_dict = {"model_type": "vae", "in_dim": in_dim, "latent_dim": latent_dim, "coord": coord,
                        "conv_encoder": conv_e, "numlayers_encoder": numlayers_e,
                        "numlayers_decoder": numlayers_d, "numhidden_encoder": numhidden_e,

@@ -124,6 +124,14 @@ class viBaseTrainer:
         eps = z_mean.new(z_mean.size(0), z_mean.size(1)).normal_()
         return z_mean + z_sd * eps
 
+    @classmethod
+    def reparameterize_discrete(cls, alpha: torch.Tensor, tau: float) -> torch.Tensor:
+        """Gumbel-Softmax sample of one discrete latent variable, the uniform noise drawn on the compute device
+        (vitrainer.py:236-248); the sample and its gradient are csrc/joint.hip."""
+        from .._joint import gumbel_softmax
+        su = alpha.new(alpha.size()).uniform_()
+        return gumbel_softmax(alpha, su, tau)
+
     def _unpack(self, batch):
         if len(batch) == 1:
             return batch[0].to(self.device), None

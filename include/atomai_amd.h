@@ -477,6 +477,31 @@ int amx_rvae_latent_fwd(const float* zmean, const float* zlogsd, const float* ep
 int amx_rvae_latent_bwd(const float* zlogsd, const float* eps, const float* dtheta, const float* dzc, int B, int Z,
                         int translation, float dx_prior, float* dmean, float* dlogsd, void* stream);
 
+/* Joint VAEs (jVAE / jrVAE): the discrete Gumbel-Softmax channel (csrc/joint.hip).  fp32, deterministic (fixed-order wave
+ * reductions, no atomics).  The H heads of sizes seg_sizes[0..H-1] (a HOST array) lie side by side in a (B, D) row,
+ * D = sum of the sizes.  Limits, enforced with a bad-argument code: 1 <= H <= AMX_JOINT_MAX_HEADS, every size >= 1,
+ * D <= AMX_JOINT_MAX_D. */
+#define AMX_JOINT_MAX_HEADS 16
+#define AMX_JOINT_MAX_D 4096
+/* alpha[b, seg] = softmax(logits[b, seg]) (max-subtracted); dlogits = alpha * (dalpha - sum_seg alpha * dalpha). */
+int amx_segsoftmax_fwd(const float* logits, const int* seg_sizes, int H, int B, float* alpha, void* stream);
+int amx_segsoftmax_bwd(const float* alpha, const float* dalpha, const int* seg_sizes, int H, int B, float* dlogits,
+                       void* stream);
+/* amx_rvae_latent_fwd extended by the discrete channel, one launch: zmean / zlogsd / eps [B][Z], alpha / u [B][D],
+ * coord in {0, 1, 3} leading latents go to theta [B][3] (as amx_rvae_latent_fwd; unused for coord 0),
+ * zdec [B][Z - coord + D] = [content latents | y of every head], y = softmax((log(alpha + 1e-12) + g) / tau),
+ * g = -log(-log(u + 1e-12) + 1e-12); kl_disc [B] = sum_h sum_k alpha (log(alpha + 1e-12) - log(1 / K_h + 1e-12)).
+ * Parts switch off: u NULL -> no sample (zdec [B][Z - coord]); kl_disc NULL -> no KL; Z = 0 -> no continuous part. */
+int amx_joint_latent_fwd(const float* zmean, const float* zlogsd, const float* eps, const float* alpha, const float* u,
+                         const int* seg_sizes, int H, int B, int Z, int coord, float dx_prior, float tau, float* theta,
+                         float* zdec, float* kl_disc, void* stream);
+/* Backward: zdec = the forward's output (sampled: it holds the D sample columns), upstream dtheta [B][3], dzdec (layout of
+ * zdec) and g_kl [B], each may be NULL (= zero).  dmean / dlogsd [B][Z]; dalpha [B][D] = the sample path
+ * y (dy - sum y dy) / tau / (alpha + 1e-12) plus the KL path g_kl (log(alpha + 1e-12) - h2 + alpha / (alpha + 1e-12)). */
+int amx_joint_latent_bwd(const float* zlogsd, const float* eps, const float* alpha, const float* zdec, const float* dtheta,
+                         const float* dzdec, const float* g_kl, const int* seg_sizes, int H, int B, int Z, int coord,
+                         float dx_prior, float tau, int sampled, float* dmean, float* dlogsd, float* dalpha, void* stream);
+
 
 /* The rDecoder kernels' activation function, element-wise: y[i] = tanh(x[i]) as the fused kernels evaluate it
  * (hardware exp + reciprocal, absolute error <= 2e-7; nn.Tanh of atomai/nets/ed.py:613-616).  For tests of that bound. */

@@ -1,5 +1,5 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) — one JSON line each, written to gpurun_out/.
-   python tools/bench_extra.py rvae|predict|dkl|losses
+   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses
 """
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -89,6 +89,67 @@ def bench_rvae(steps=10, warmup=3, B=512, emit=True, ab=True):
         out["ab_other_variant"] = {"backward_variant": "recompute" if saved_default else "saved activations",
                                    "ms_per_step": round(dt2 * 1e3, 3), "fwd_ms": round(tf2, 3), "bwd_ms": round(tb2, 3),
                                    "patches_per_s": round(B / dt2, 1)}
+    if emit:
+        print(json.dumps(out), flush=True)
+    return out
+
+
+def bench_jrvae(steps=10, warmup=4, reps=5, B=512, emit=True):
+    """jrVAE((64, 64), latent_dim=2, discrete_dim=[10]) training step at bs 512 next to the rVAE step of configs[3], in ONE
+    process and interleaved: rounds of `steps` steps of (rvae, jrvae on the default one-launch latent path, jrvae on the
+    step-by-step path), each round closed by a device synchronise; the median of the rounds is reported.  The
+    step-by-step path is selected the way a user would: an instance-level ``reparameterize_discrete``."""
+    from atomai_amd.trainers.trainer import _EarlyScalar
+    rs = np.random.RandomState(0)
+    X = rs.rand(B * 2, 64, 64).astype(np.float32)
+    xs = [torch.from_numpy(X[i * B:(i + 1) * B]).cuda() for i in range(2)]
+    rv = aoi.models.rVAE((64, 64), latent_dim=2, seed=0)
+    jr = aoi.models.jrVAE((64, 64), latent_dim=2, discrete_dim=[10], seed=0)
+    for m in (rv, jr):
+        m.dx_prior, m.kdict_["phi_prior"] = 0.1, 0.1
+        m.compile_trainer((X, None), None, batch_size=B)
+    stock = type(jr).reparameterize_discrete
+
+    def step(m, i):                                   # the body of viBaseTrainer.train_epoch for one mini-batch
+        m.optim.zero_grad()
+        elbo = m.forward_compute_elbo(xs[i % 2])
+        early = _EarlyScalar(elbo)
+        (-elbo).backward()
+        m.optim.step()
+        return early.item()
+
+    def select(name):
+        jr.__dict__.pop("reparameterize_discrete", None)
+        if name == "jrvae_step_by_step":
+            jr.reparameterize_discrete = stock
+        assert jr._default_sampling() == (name != "jrvae_step_by_step")
+        return rv if name == "rvae" else jr
+    variants = ["rvae", "jrvae_default", "jrvae_step_by_step"]
+    for name in variants:
+        m = select(name)
+        for i in range(warmup):
+            step(m, i)
+    times, last = {name: [] for name in variants}, {}
+    for _ in range(reps):
+        for name in variants:
+            m = select(name)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for i in range(steps):
+                last[name] = step(m, i)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / steps * 1e3)
+    select("jrvae_default")
+    med = {name: float(np.median(t)) for name, t in times.items()}
+    out = {"metric": "jrVAE training step (64x64, bs=512, latent_dim=2, discrete_dim=[10])", "unit": "ms",
+           "value": round(med["jrvae_default"], 3), "higher_is_better": False, "n_gpus": 1, "dtype": "f32",
+           "patches_per_s": round(B / med["jrvae_default"] * 1e3, 1),
+           "rvae_ms_per_step_same_process": round(med["rvae"], 3),
+           "jrvae_minus_rvae_ms": round(med["jrvae_default"] - med["rvae"], 3),
+           "ab_latent_path": {"one_launch_ms": round(med["jrvae_default"], 3),
+                              "step_by_step_ms": round(med["jrvae_step_by_step"], 3)},
+           "rounds_ms": {name: [round(t, 3) for t in ts] for name, ts in times.items()},
+           "elbo": {name: round(v, 3) for name, v in last.items()},
+           "note": f"medians of {reps} interleaved rounds of {steps} steps after {warmup} warm-up steps per variant"}
     if emit:
         print(json.dumps(out), flush=True)
     return out
@@ -508,6 +569,6 @@ if __name__ == "__main__":
     os.makedirs("gpurun_out", exist_ok=True)
     res = {}
     for w in what:
-        res[w] = {"rvae": bench_rvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "segfamily": bench_segfamily, "losses": bench_losses,
+        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "segfamily": bench_segfamily, "losses": bench_losses,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)
