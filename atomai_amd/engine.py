@@ -14,6 +14,7 @@ the kernels.  No CPU fallback exists; `_lib` raises if the extension is missing.
 from __future__ import annotations
 
 import ctypes
+import os
 import weakref
 from typing import Dict, List, Optional, Sequence
 
@@ -24,22 +25,32 @@ from . import _lib as L
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 
-import os as _os
-# Backward fusion switches, chosen by measurement:
+# ---- host-side switches.  Plain module attributes read at every use: tests and tools/gpu_step_ab.py assign to them.
+# AMX_FUSE has one bit, chosen by measurement:
 #   2: BN-backward sums emitted by the pool / px backward kernels that write the final dy   (default: on)
-#   4: dpre formed in the wgrad loader (experiment; off)
 # Interleaved in-process A/B on MI355X in round 1 (U-Net bs 32 512^2, ms/step, min of 3):
 #   0: 20.76   2: 20.22   [dgrad-loader / dgrad-epilogue fusions, bits 1 and 8: 21.22 - 22.40]
 # -> moving the HBM-bound BatchNorm-backward passes INTO the MFMA kernels costs them more (registers ->
 #    fewer co-resident workgroups, exposed load latency) than the removed passes save.  Bits 1 and 8 (fusion into the
 #    data-gradient kernel) were removed in round 2 together with their register cost in the convolution kernel.
-FUSE = int(_os.environ.get("AMX_FUSE", "2")) & 6
-# first-layer weight gradient on the main stream (host-side switch, read once; tools/gpu_step_ab.py re-reads it for A/B)
-FIRST_WGRAD_MAIN = _os.environ.get("AMX_FIRST_WGRAD_MAIN", "1") != "0"
-# data gradient of a two-source layer as one wave-specialised launch per source where the kernel takes them singly (host-side)
-DGRAD_SPLIT = _os.environ.get("AMX_DGRAD_SPLIT", "1") != "0"
+FUSE = int(os.environ.get("AMX_FUSE", "2")) & 2
+# first-layer weight gradient on the main stream (tools/gpu_step_ab.py re-reads it for A/B)
+FIRST_WGRAD_MAIN = os.environ.get("AMX_FIRST_WGRAD_MAIN", "1") != "0"
+# data gradient of a two-source layer as one wave-specialised launch per source where the kernel takes them singly
+DGRAD_SPLIT = os.environ.get("AMX_DGRAD_SPLIT", "1") != "0"
 # pooling backward fused with the first layer's weight gradient (amx_pool2x2_bwd_wgrad1): dy of that layer never reaches HBM
-FUSE_POOL_WGRAD1 = _os.environ.get("AMX_FUSE_POOL_WGRAD1", "1") != "0"
+FUSE_POOL_WGRAD1 = os.environ.get("AMX_FUSE_POOL_WGRAD1", "1") != "0"
+# UpsampleBlock forward in one pass (csrc/upconv.hip): AMX_FUSE_UPCONV=0 keeps the two launches
+FUSE_UPCONV = os.environ.get("AMX_FUSE_UPCONV", "1") != "0"
+UPCONV_MIN_PIXELS = 1 << 19      # low-res pixels of the launch from which the one-pass kernel wins (profiles/r05_logs/r05_upconv_ab4.log:
+#                                  x16 512^2 949 -> 731 us, x32 256^2 253 -> 170, x32 128^2 122 -> 108; x32 64^2 69 vs 73: two kernels)
+# experiment switch for the eval-mode epilogue fusions (classification head, DilatedBlock sum); 0 = separate kernels
+FUSE_HEAD = os.environ.get("AMX_FUSE_HEAD", "1") != "0"
+# Eval mode: the 2x2 max-pool that follows a one-layer first block (Unet / dilnet c1) is produced by the first-layer kernel
+# (amx_conv1_fwd_pool); AMX_FUSE_POOL=0 keeps the separate amx_pool2x2_fwd launch (A/B switch, tools/gpu_step_ab.py).
+FUSE_POOL = os.environ.get("AMX_FUSE_POOL", "1") != "0"
+# the training step's head, loss and their backward in one pass (PxLossNode); AMX_FUSE_PX_LOSS=0 keeps the logits
+FUSE_PX_LOSS = os.environ.get("AMX_FUSE_PX_LOSS", "1") != "0"
 
 
 def bwd_fuse_enabled() -> bool:
@@ -85,7 +96,7 @@ class Act:
         self.gx: Optional[torch.Tensor] = None        # DilatedBlock's shared extra gradient
         self.unmasked: Optional[torch.Tensor] = None  # DilatedBlock + training Dropout: lrelu(conv) BEFORE the mask
         self.pooled: Optional["Act"] = None           # eval mode: max_pool2d of this (normalised) activation, already computed
-        self.wg1 = None                               # output of the net's FIRST layer (training): (net input [N,1,H,W], slope)
+        self.wg1 = None                               # output of the net's FIRST layer (training): (net input [N,1,H,W], slope, dilation)
                                                       # -> the pooling backward may form that layer's weight-gradient sums
         self.wg1_parts = None                         # ... and leaves them here: (part3 [rows][3][10][Cs], rows)
         self.needs_grad = needs_grad
@@ -267,13 +278,55 @@ class _Node:
         raise NotImplementedError
 
 
+def _chunk_rows(rows: int, nch: int) -> int:
+    """Rows that remain once `rows` rows have been summed in chunks of ceil(rows / nch) (at most `nch` of them)."""
+    return -(-rows // -(-rows // nch))
+
+
+def _reduce_chunks(part: torch.Tensor, rows: int, ncols: int, nch: int):
+    """First stage of a deterministic two-stage row reduction: [rows][ncols] -> ([<= nch][ncols], rows that remain).
+    The callers decide from which row count on it pays and how many chunks to use (measured per site)."""
+    tmp = _empty((nch, ncols), part)
+    L.call("amx_reduce_rows_chunked", L.ptr(part), rows, ncols, nch, L.ptr(tmp), _sp(part))
+    return tmp, _chunk_rows(rows, nch)
+
+
+def _two_sources(srcs: Sequence["Act"]):
+    """(s0, s1 or None, N, H, W, C0, C0s, C1, C1s) of a layer over one source or the concatenation of two."""
+    s0 = srcs[0]
+    s1 = srcs[1] if len(srcs) > 1 else None
+    C1, C1s = (s1.C, s1.Cs) if s1 else (0, 0)
+    return s0, s1, s0.N, s0.H, s0.W, s0.C, s0.Cs, C1, C1s
+
+
+def _src_args(s0: "Act", s1: Optional["Act"], slopes: bool = False) -> tuple:
+    """Leading arguments of the two-source convolution entry points: per source (tensor, pending scale, pending shift,
+    [its post-affine LeakyReLU slope,] padded channels); nulls and 0 channels for a missing second source."""
+    a0 = (L.ptr(s0.t), L.ptr(s0.scale), L.ptr(s0.shift))
+    a1 = (L.ptr(s1.t if s1 else None), L.ptr(s1.scale if s1 else None), L.ptr(s1.shift if s1 else None))
+    C1s = s1.Cs if s1 else 0
+    if slopes:
+        return a0 + (s0.post_slope, s0.Cs) + a1 + (s1.post_slope if s1 else 1.0, C1s)
+    return a0 + (s0.Cs,) + a1 + (C1s,)
+
+
+def _has_input_slope(s0: "Act", s1: Optional["Act"]) -> bool:
+    return s0.post_slope != 1.0 or (s1 is not None and s1.post_slope != 1.0)
+
+
+# How a layer's data gradient is launched (ConvNode._dgrad_plan)
+DGRAD_NONE = "none"                  # no source wants a gradient
+DGRAD_GENERAL = "general"            # amx_conv2d_dgrad over a materialised dpre
+DGRAD_WS = "ws"                      # one launch of the wave-specialised kernel, dpre formed by its loader
+DGRAD_WS_SPLIT = "ws-split"          # two such launches, one per source of a concatenation
+
+
 class ConvNode(_Node):
     """conv (3x3 / dilated / 1x1) [+bias] [+LeakyReLU] [+BatchNorm statistics] over 1 or 2 sources."""
 
-    def __init__(self, tape, srcs: Sequence[Act], conv, bn, slope: float, x_plain=None, post_slope: float = 1.0,
-                 drop_p: float = 0.0, keep_unmasked: bool = False, pool_next: bool = False):
+    def __init__(self, tape, srcs: Sequence[Act], conv, bn, slope: float, post_slope: float = 1.0,
+                 drop_p: float = 0.0, keep_unmasked: bool = False):
         self.srcs = list(srcs)
-        self.pool_next = pool_next                    # first layer whose output goes straight into a 2x2 max-pool
         self.keep_unmasked = keep_unmasked            # DilatedBlock sums the convolution output itself too
         self.conv, self.bn, self.slope = conv, bn, float(slope)
         # training-mode nn.Dropout between the convolution and its LeakyReLU (blocks.py:68-69): applied after the fused
@@ -286,7 +339,6 @@ class ConvNode(_Node):
             assert self.slope == 1.0
             self.slope, self.post_slope = self.post_slope, 1.0
         assert self.post_slope == 1.0 or self.slope == 1.0, "one activation per layer"
-        self.x_plain = x_plain                           # (N,1,H,W) tensor for the Cin==1 kernel
         w = conv.weight
         self.cout = w.shape[0]
         self.taps = w.shape[2] * w.shape[3]
@@ -303,333 +355,231 @@ class ConvNode(_Node):
         self.out = self._forward(tape)
         self.out.post_slope = self.post_slope
         self.out.producer = self.bn is not None and self.post_slope == 1.0
-        # the net's first layer in training (1 input channel, 3x3, BatchNorm, no dropout mask): its consumer's pooling
-        # backward may fuse this layer's weight gradient (PoolNode.backward, amx_pool2x2_bwd_wgrad1)
-        if (FUSE_POOL_WGRAD1 and self.x_plain is not None and self.bn is not None and tape.training and tape.need_grad
-                and self.mask is None and self.post_slope == 1.0 and self.taps == 9 and self.x_plain.shape[1] == 1
-                and bwd_fuse_enabled() and bool(FUSE & 2) and not (FUSE & 4)):      # (FUSE & 4: the experiment mode that
-            self.out.wg1 = (self.x_plain, float(self.slope))                            #  materialises dpre from the real dy)
 
     # -------------------------------------------------------------------------------- forward
     def _forward(self, tape) -> Act:
-        w, b = self.conv.weight, self.conv.bias
-        cos, cop = r4(self.cout), r16(self.cout)
-        training_bn = self.bn is not None and tape.training
+        want_stats = self.bn is not None and tape.training
         drop = self.drop_p > 0.0
-        want_stats = training_bn
+        # with dropout the BatchNorm statistics are those of the MASKED tensor: amx_dropout_fwd emits them instead
+        y, stats, stat_mode, lat = self._conv_fwd(tape, want_stats and not drop)
+        unmasked = None
         if drop:
-            training_bn = False                              # the statistics are those of the MASKED tensor (below)
-        if self.x_plain is not None:
-            x = self.x_plain
-            N, _, H, W = x.shape
-            y = _empty((N, H, W, cos), x)
-            npix = N * H * W
-            self.rows = L.load().amx_rows_for(npix)
-            self.rows_pix = L.load().amx_rows_pix(npix)
-            stats = _empty((self.rows, 2, cop), x) if training_bn else None
-            norm = tape.input_norm if tape.input_norm is not None else (0.0, 1.0)
-            tape.input_norm_used = tape.input_norm is not None
-            self.pooled = None
-            if (self.pool_next and FUSE_POOL and self.bn is not None and not tape.training and not tape.need_grad
-                    and not drop and L.load().amx_conv1_fwd_pool_supported(H, W, self.dil, self.rows_pix)):
-                # eval mode: the 2x2 max-pool of the normalised output comes out of the same kernel (fcnn.py:123, 219)
-                psc, psh = bn_eval_affine(self.bn, self.cout, cos, y)
-                self.pooled = _empty((N, H // 2, W // 2, cos), x)
-                L.call("amx_conv1_fwd_pool", L.ptr(x), L.ptr(w.detach()), L.ptr(b.detach() if b is not None else None),
-                       L.ptr(y), L.ptr(self.pooled), L.ptr(psc), L.ptr(psh), N, H, W, self.cout, cos, self.dil,
-                       self.slope, self.rows, self.rows_pix, float(norm[0]), float(norm[1]), _sp(x))
-            else:
-                L.call("amx_conv1_fwd", L.ptr(x), L.ptr(w.detach()), L.ptr(b.detach() if b is not None else None),
-                       L.ptr(y), L.ptr(stats), N, H, W, self.cout, cos, self.dil, self.slope, self.rows,
-                       self.rows_pix, float(norm[0]), float(norm[1]), _sp(x))
-            stat_mode, lat = 1, 0
-        else:
-            s0 = self.srcs[0]
-            s1 = self.srcs[1] if len(self.srcs) > 1 else None
-            N, H, W = s0.N, s0.H, s0.W
-            C0, C0s = s0.C, s0.Cs
-            C1, C1s = (s1.C, s1.Cs) if s1 else (0, 0)
-            assert w.shape[1] == C0 + C1, "channel mismatch between conv weight and its sources"
-            wpk = pack_weights(w, C0, C0s, C1, C1s, self.taps, 0)
-            bias = b.detach() if b is not None else None
-            y = _empty((N, H, W, cos), s0.t)
-            th = L.load().amx_conv2d_tile_h(C0s + C1s, self.cout, self.taps, self.dil, H)
-            self.rows = L.load().amx_conv2d_stats_rows(C0s + C1s, self.cout, self.taps, self.dil, N, H, W)
-            self.rows_pix = th                               # modes 0 / 3: the rows one wave owns
-            lat = L.load().amx_conv2d_stats_lattice(self.taps, self.dil)
-            stats = _empty((self.rows, 2, cop), s0.t) if training_bn else None
-            ps0, ps1 = s0.post_slope, (s1.post_slope if s1 else 1.0)
-            if ps0 != 1.0 or ps1 != 1.0:
-                L.call("amx_conv2d_fwd_act", L.ptr(s0.t), L.ptr(s0.scale), L.ptr(s0.shift), ps0, C0s,
-                       L.ptr(s1.t if s1 else None), L.ptr(s1.scale if s1 else None),
-                       L.ptr(s1.shift if s1 else None), ps1, C1s, L.ptr(wpk), L.ptr(bias), None,
-                       L.ptr(y), cos, None, 0, L.ptr(stats), N, H, W, self.cout, self.taps, self.dil,
-                       self.slope, _sp(y))
-            else:
-                L.call("amx_conv2d_fwd", L.ptr(s0.t), L.ptr(s0.scale), L.ptr(s0.shift), C0s,
-                       L.ptr(s1.t if s1 else None), L.ptr(s1.scale if s1 else None),
-                       L.ptr(s1.shift if s1 else None), C1s, L.ptr(wpk), L.ptr(bias), None,
-                       L.ptr(y), cos, None, 0, L.ptr(stats), N, H, W, self.cout, self.taps, self.dil,
-                       self.slope, _sp(y))
-            stat_mode = 3 if lat else 0                      # 3: rows ordered by residue class (dilated layers)
-        if drop:
-            npix = N * H * W
-            self.rows = L.load().amx_rows_for(npix)
-            self.rows_pix = L.load().amx_rows_pix(npix)
-            stats = _empty((self.rows, 2, cop), y) if want_stats else None
-            self.mask = _empty(y.shape, y)
-            unmasked = y.clone() if self.keep_unmasked else None
-            hook = DROPOUT_MASK_HOOK[0]
-            mask_in = hook(tuple(y.shape), self.drop_p).to(y.device).float().contiguous() if hook else None
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())          # CPU generator: reproducible under manual_seed
-            if torch.distributed.is_available() and torch.distributed.is_initialized():
-                seed ^= torch.distributed.get_rank() << 48             # data-parallel ranks draw different masks
-            L.call("amx_dropout_fwd", L.ptr(y), L.ptr(self.mask), L.ptr(mask_in), self.drop_p, seed, L.ptr(stats),
-                   npix, cos, cop, self.rows, self.rows_pix, _sp(y))
-            stat_mode = 1
-            training_bn = want_stats
+            stats, stat_mode, unmasked = self._dropout_fwd(y, want_stats)
         scale = shift = None
         if self.bn is not None:
-            bn = self.bn
-            if tape.training:
-                scale, shift = _empty((cos,), y), _empty((cos,), y)
-                _bn_generation[0] += 1
-                self.save_mean, self.save_invstd = _empty((cos,), y), _empty((cos,), y)
-                mom = BN_MOMENTUM if bn.momentum is None else bn.momentum
-                nrows = self.rows
-                if nrows > 512 or stat_mode == 3:                  # two-stage merge: coalesced chunk merge, then per channel
-                    nch = max(1, min(1024, nrows // 32))           # (the only consumer of the lattice row order)
-                    merged = _empty((nch, 3, cop), y)
-                    L.call("amx_bn_stats_merge", L.ptr(stats), nrows, cop, stat_mode, N, H, W,
-                           self.rows_pix, lat if stat_mode == 3 else 1, nch, L.ptr(merged), _sp(y))
-                    stats, nrows, stat_mode = merged, -(-nrows // -(-nrows // nch)), 2
-                L.call("amx_bn_finalize", L.ptr(stats), nrows, cop, stat_mode, N, H, W, self.rows_pix,
-                       L.ptr(bn.weight.detach()), L.ptr(bn.bias.detach()), L.ptr(bn.running_mean),
-                       L.ptr(bn.running_var), mom, bn.eps, self.cout, cos, L.ptr(scale), L.ptr(shift),
-                       L.ptr(self.save_mean), L.ptr(self.save_invstd), _sp(y))
-                if bn.num_batches_tracked is not None:
-                    tape.bn_counters.append(bn.num_batches_tracked)      # += 1 for all layers in ONE launch
-            else:
-                scale, shift = bn_eval_affine(bn, self.cout, cos, y)
-        needs = tape.need_grad
-        act = Act(y, self.cout, scale, shift, needs_grad=needs)
-        if self.x_plain is not None and self.pooled is not None:
-            act.pooled = Act(self.pooled, self.cout, needs_grad=False)
-        if drop and self.keep_unmasked:
-            act.unmasked = unmasked
+            scale, shift = self._bn_fwd(tape, y, stats, stat_mode, lat)
+        act = Act(y, self.cout, scale, shift, needs_grad=tape.need_grad)
+        act.unmasked = unmasked
         return act
+
+    def _conv_fwd(self, tape, want_stats: bool):
+        """The convolution launch -> (y, per-block statistics rows or None, their row order, lattice); sets the
+        (rows, rows_pix) those statistics were emitted with."""
+        w, b = self.conv.weight, self.conv.bias
+        cos, cop = r4(self.cout), r16(self.cout)
+        s0, s1, N, H, W, C0, C0s, C1, C1s = _two_sources(self.srcs)
+        assert w.shape[1] == C0 + C1, "channel mismatch between conv weight and its sources"
+        wpk = pack_weights(w, C0, C0s, C1, C1s, self.taps, 0)
+        bias = b.detach() if b is not None else None
+        y = _empty((N, H, W, cos), s0.t)
+        th = L.load().amx_conv2d_tile_h(C0s + C1s, self.cout, self.taps, self.dil, H)
+        self.rows = L.load().amx_conv2d_stats_rows(C0s + C1s, self.cout, self.taps, self.dil, N, H, W)
+        self.rows_pix = th                               # modes 0 / 3: the rows one wave owns
+        lat = L.load().amx_conv2d_stats_lattice(self.taps, self.dil)
+        stats = _empty((self.rows, 2, cop), s0.t) if want_stats else None
+        act = _has_input_slope(s0, s1)
+        L.call("amx_conv2d_fwd_act" if act else "amx_conv2d_fwd", *_src_args(s0, s1, slopes=act), L.ptr(wpk),
+               L.ptr(bias), None, L.ptr(y), cos, None, 0, L.ptr(stats), N, H, W, self.cout, self.taps, self.dil,
+               self.slope, _sp(y))
+        return y, stats, (3 if lat else 0), lat              # 3: rows ordered by residue class (dilated layers)
+
+    def _dropout_fwd(self, y, want_stats: bool):
+        """Masks y in place (the mask is kept for backward) -> (statistics rows of the masked tensor or None, their row
+        order, the un-masked copy a DilatedBlock sums)."""
+        N, H, W, cos = y.shape
+        npix, cop = N * H * W, r16(self.cout)
+        self.rows = L.load().amx_rows_for(npix)
+        self.rows_pix = L.load().amx_rows_pix(npix)
+        stats = _empty((self.rows, 2, cop), y) if want_stats else None
+        self.mask = _empty(y.shape, y)
+        unmasked = y.clone() if self.keep_unmasked else None
+        hook = DROPOUT_MASK_HOOK[0]
+        mask_in = hook(tuple(y.shape), self.drop_p).to(y.device).float().contiguous() if hook else None
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())          # CPU generator: reproducible under manual_seed
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            seed ^= torch.distributed.get_rank() << 48             # data-parallel ranks draw different masks
+        L.call("amx_dropout_fwd", L.ptr(y), L.ptr(self.mask), L.ptr(mask_in), self.drop_p, seed, L.ptr(stats),
+               npix, cos, cop, self.rows, self.rows_pix, _sp(y))
+        return stats, 1, unmasked
+
+    def _bn_fwd(self, tape, y, stats, stat_mode: int, lat: int):
+        """(scale, shift) of the layer's BatchNorm: from the batch statistics in training (merged per channel, running
+        statistics updated, mean / invstd kept for backward), the cached eval affine otherwise."""
+        bn = self.bn
+        N, H, W, cos = y.shape
+        if not tape.training:
+            return bn_eval_affine(bn, self.cout, cos, y)
+        cop = r16(self.cout)
+        scale, shift = _empty((cos,), y), _empty((cos,), y)
+        _bn_generation[0] += 1
+        self.save_mean, self.save_invstd = _empty((cos,), y), _empty((cos,), y)
+        mom = BN_MOMENTUM if bn.momentum is None else bn.momentum
+        nrows = self.rows
+        if nrows > 512 or stat_mode == 3:                  # two-stage merge: coalesced chunk merge, then per channel
+            nch = max(1, min(1024, nrows // 32))           # (the only consumer of the lattice row order)
+            merged = _empty((nch, 3, cop), y)
+            L.call("amx_bn_stats_merge", L.ptr(stats), nrows, cop, stat_mode, N, H, W,
+                   self.rows_pix, lat if stat_mode == 3 else 1, nch, L.ptr(merged), _sp(y))
+            stats, nrows, stat_mode = merged, _chunk_rows(nrows, nch), 2
+        L.call("amx_bn_finalize", L.ptr(stats), nrows, cop, stat_mode, N, H, W, self.rows_pix,
+               L.ptr(bn.weight.detach()), L.ptr(bn.bias.detach()), L.ptr(bn.running_mean),
+               L.ptr(bn.running_var), mom, bn.eps, self.cout, cos, L.ptr(scale), L.ptr(shift),
+               L.ptr(self.save_mean), L.ptr(self.save_invstd), _sp(y))
+        if bn.num_batches_tracked is not None:
+            tape.bn_counters.append(bn.num_batches_tracked)      # += 1 for all layers in ONE launch
+        return scale, shift
 
     # -------------------------------------------------------------------------------- backward
     def backward(self, tape) -> None:
-        """BatchNorm backward: per-channel sums (emitted by the pool / px backward kernel that wrote the final dy, or
-        by amx_bn_bwd_reduce) -> amx_bn_bwd_finalize -> dpre = lrelu'(a) * (k1*dy + k2*a + k3) materialised by
-        amx_bn_bwd_apply; then the weight gradient (side stream) and the data gradient read dpre."""
         out = self.out
         dy = out.grad if out.grad is not None else out.gx
-        if dy is None:
-            return                                        # output never used downstream
+        if dy is not None:                                # else: output never used downstream
+            self._backward(tape, out, dy)
+
+    def _backward(self, tape, out: Act, dy: torch.Tensor) -> None:
+        """BatchNorm backward: per-channel sums (emitted by the pool / px backward kernel that wrote the final dy, or
+        by amx_bn_bwd_reduce) -> amx_bn_bwd_finalize -> dpre = lrelu'(a) * (k1*dy + k2*a + k3), either formed by the
+        loaders of both consumers or materialised once by amx_bn_bwd_apply; then the weight gradient and the data
+        gradient read it.  `out` is the activation this layer wrote and `dy` its gradient."""
         a = out.t
-        npix, cos = out.npix, out.Cs
-        sp = _sp(a)
-        has_bias = self.conv.bias is not None
         if self.bn is not None and not tape.training:
             raise L.AmxError("backward through eval-mode BatchNorm is not on the hot path")
         if self.post_slope != 1.0:
-            # consumers saw LeakyReLU(scale*a + shift): first back through that activation, then the usual
-            # BatchNorm backward (with an identity epilogue activation, self.slope == 1)
-            assert out.gx is None
-            masked = _empty(a.shape, a)
-            L.call("amx_lrelu_bwd", L.ptr(dy), L.ptr(a), L.ptr(out.scale), L.ptr(out.shift), self.post_slope,
-                   npix, cos, L.ptr(masked), None, sp)
-            dy = masked
-        fused = out.gx is None and bool(FUSE & 4) and self.mask is None
-        # Round 4: layers whose data gradient runs on the wave-specialised kernel form dpre inside BOTH consumers' loaders
-        # (amx_conv2d_dgrad_fused / amx_conv2d_wgrad_fused) — no amx_bn_bwd_apply pass, dpre never exists in HBM.
-        fused_ws = (not fused and self._bwd_fusable(out)) if self.bn is not None else False
-        # the net's FIRST layer has no data gradient: its BatchNorm backward is only read by the first-layer weight-gradient
-        # kernel, which forms it while loading (amx_conv1_wgrad_fused) — the 512^2 x 16-channel apply pass of U-Net's c1
-        # (0.32 ms at the very end of the backward pass, nothing left to overlap it) is not launched at all
-        if (not fused and self.bn is not None and self.x_plain is not None and self.mask is None and out.gx is None
-                and self.post_slope == 1.0 and bwd_fuse_enabled()):
-            fused_ws = True
-        fused = fused or fused_ws
-        k = None
+            dy = self._post_act_bwd(out, dy)
+        plan = self._dgrad_plan(out)
+        on_load = self._dpre_on_load(out, plan)
+        k = self._bn_bwd_sums(tape, out, dy) if self.bn is not None else None
+        want_bias = self.conv.bias is not None            # True: the weight-gradient kernel emits the bias gradient
         aux = None
-        bias_part = None
-        if self.bn is not None:
-            bn = self.bn
-            if out.bstats is not None:
-                part, rows, stride, off = out.bstats
-                part_ptr = part.view(-1)[off:]
-            else:
-                rows = L.load().amx_rows_for(npix)
-                part = _empty((rows, 2, cos), a)
-                L.call("amx_bn_bwd_reduce", L.ptr(dy), L.ptr(a), npix, cos, L.ptr(part), sp)
-                part_ptr, stride = part, cos
-            dgamma, dbeta = grad_buffer(bn.weight, a), grad_buffer(bn.bias, a)
-            k = _empty((3, cos), a)
-            L.call("amx_bn_bwd_finalize", L.ptr(part_ptr), rows, stride, cos, self.cout, npix,
-                   L.ptr(bn.weight.detach()), L.ptr(self.save_mean), L.ptr(self.save_invstd),
-                   L.ptr(dgamma), L.ptr(dbeta), L.ptr(k[0]), L.ptr(k[1]), L.ptr(k[2]), sp)
-            tape.add_param_grad(bn.weight, dgamma)
-            tape.add_param_grad(bn.bias, dbeta)
-        needs_transform = self.bn is not None or self.slope != 1.0 or out.gx is not None
-        dpre_mat = None
-        if needs_transform and fused and not fused_ws:
-            # experiment mode: one of the two consumers still wants a materialised dpre
-            arows = L.load().amx_rows_for(npix)
-            bias_part = _empty((arows, cos), a) if has_bias else None
-            dpre_mat = _empty(a.shape, a)
-            kk = (L.ptr(k[0]), L.ptr(k[1]), L.ptr(k[2])) if k is not None else (None, None, None)
-            L.call("amx_bn_bwd_apply", L.ptr(dy), L.ptr(a), L.ptr(out.gx), *kk, self.slope, npix, cos,
-                   L.ptr(dpre_mat), L.ptr(bias_part), sp)
-        if needs_transform and fused:
-            aux, dpre = a, dy                               # transformed on load inside wgrad / dgrad
-        elif needs_transform:
-            arows = L.load().amx_rows_for(npix)
-            bias_part = _empty((arows, cos), a) if (has_bias and self.mask is None) else None
-            dpre = _empty(a.shape, a)
-            kk = (L.ptr(k[0]), L.ptr(k[1]), L.ptr(k[2])) if k is not None else (None, None, None)
-            L.call("amx_bn_bwd_apply", L.ptr(dy), L.ptr(a), L.ptr(out.gx), *kk, self.slope, npix, cos,
-                   L.ptr(dpre), L.ptr(bias_part), sp)
-            k = None
-            if self.mask is not None:
-                # d conv = mask * lrelu'(.) * (...): the saved activation is already masked, so the sign test of
-                # bn_bwd_apply is right wherever the mask is non-zero, and the mask zeroes the rest
-                L.call("amx_dropout_bwd", L.ptr(dpre), L.ptr(self.mask), dpre.numel(), sp)
-                if out.gx is not None:        # DilatedBlock: the convolution output itself is a summed sub-layer too
-                    L.call("amx_add_inplace", L.ptr(dpre), L.ptr(out.gx), dpre.numel(), sp)
-                if has_bias:                                  # bias gradient = column sums of the masked dpre
-                    nch = 128 if npix >= 1024 else 1
-                    tmp = _empty((nch, cos), a)
-                    L.call("amx_reduce_rows_chunked", L.ptr(dpre), npix, cos, nch, L.ptr(tmp), sp)
-                    db = grad_buffer(self.conv.bias, a)
-                    L.call("amx_reduce_rows", L.ptr(tmp), -(-npix // -(-npix // nch)), cos, self.cout, 1.0, L.ptr(db), sp)
-                    tape.add_param_grad(self.conv.bias, db)
-                    has_bias = False                          # done: neither bias_part nor the wgrad kernel adds it
+        if on_load:
+            aux, dpre = a, dy                             # transformed on load inside wgrad / dgrad
+        elif self.bn is not None or self.slope != 1.0 or out.gx is not None:
+            dpre = self._materialise_dpre(tape, out, dy, k)
+            k, want_bias = None, False
         else:
             assert self.mask is None, "dropout without an activation is not a layer of the reference's blocks"
-            dpre = dy                                       # linear convolution (1x1 of UpsampleBlock)
-        if bias_part is not None:
-            db = grad_buffer(self.conv.bias, a)
-            L.call("amx_reduce_rows", L.ptr(bias_part), bias_part.shape[0], cos, self.cout, 1.0, L.ptr(db), sp)
-            tape.add_param_grad(self.conv.bias, db)
+            dpre = dy                                     # linear convolution (1x1 of UpsampleBlock)
         kptr = (k[0], k[1], k[2]) if k is not None else (None, None, None)
-        w = self.conv.weight
-        dw = grad_buffer(w, a)
-        want_bias = has_bias and bias_part is None
-        # The weight gradient (MFMA-bound) has no consumer inside backward: side stream.
-        w_in = (dpre, aux, kptr)
-        d_in = (dpre, aux, kptr) if dpre_mat is None else (dpre_mat, None, (None, None, None))
-        # (enqueued BEFORE the layer's data gradient; after it, or on the main stream, measured no different / slower:
-        #  profiles/r04_wgrad_ws.md.  Tape.use_side_stream = False serialises everything for the per-kernel timing pass.)
-        if self.x_plain is not None and FIRST_WGRAD_MAIN:
-            # The net's first layer is the LAST node of backward: nothing follows on the main stream, while the side stream
-            # still drains its backlog of weight gradients — this one runs on the (idle) main stream beside them (round 6:
-            # the step used to end with conv1_wgrad queued behind c2.0's weight gradient, profiles/r06_step_timeline_final.txt)
-            self._wgrad(tape, w_in[0], w_in[1], w_in[2], dw, a, want_bias)
-            return
-        with tape.side(a, keep=(dpre, dy, a, k, dpre_mat)):
-            self._wgrad(tape, w_in[0], w_in[1], w_in[2], dw, a, want_bias)
-        if self.x_plain is not None:
-            return
-        s0 = self.srcs[0]
-        s1 = self.srcs[1] if len(self.srcs) > 1 else None
-        N, H, W = s0.N, s0.H, s0.W
-        C0, C0s = s0.C, s0.Cs
-        C1, C1s = (s1.C, s1.Cs) if s1 else (0, 0)
-        self._dgrad(tape, d_in[0], d_in[1], d_in[2], s0, s1, N, H, W, C0, C0s, C1, C1s, cos, sp)
+        dw = grad_buffer(self.conv.weight, a)
+        if self._wgrad_on_main():
+            self._wgrad(tape, out, dpre, aux, kptr, dw, want_bias)
+        else:
+            # The weight gradient (MFMA-bound) has no consumer inside backward: side stream.
+            # (enqueued BEFORE the layer's data gradient; after it, or on the main stream, measured no different / slower:
+            #  profiles/r04_wgrad_ws.md.  Tape.use_side_stream = False serialises everything for the per-kernel timing pass.)
+            with tape.side(a, keep=(dpre, dy, a, k)):
+                self._wgrad(tape, out, dpre, aux, kptr, dw, want_bias)
+        if plan != DGRAD_NONE:
+            self._dgrad(tape, plan, out.Cs, dpre, aux, kptr)
 
-    def _bwd_fusable(self, out) -> bool:
-        """True when this layer's BatchNorm / LeakyReLU backward can be formed inside the loaders of its two consumers
-        (round 4): the data gradient must be a launch of the wave-specialised kernel writing fresh gradients (no
-        accumulation into an existing one), nothing else may be folded into dpre (dropout mask, DilatedBlock sum)."""
-        if self.x_plain is not None or self.mask is not None or out.gx is not None or self.post_slope != 1.0:
-            return False
-        if not self.srcs or len(self.srcs) > 2:
-            return False
-        s0 = self.srcs[0]
-        s1 = self.srcs[1] if len(self.srcs) > 1 else None
+    def _wgrad_on_main(self) -> bool:
+        return False
+
+    def _post_act_bwd(self, out: Act, dy):
+        """Consumers saw LeakyReLU(scale*a + shift): first back through that activation, then the usual BatchNorm
+        backward (with an identity epilogue activation, self.slope == 1)."""
+        assert out.gx is None
+        masked = _empty(out.t.shape, out.t)
+        L.call("amx_lrelu_bwd", L.ptr(dy), L.ptr(out.t), L.ptr(out.scale), L.ptr(out.shift), self.post_slope,
+               out.npix, out.Cs, L.ptr(masked), None, _sp(out.t))
+        return masked
+
+    def _bn_bwd_sums(self, tape, out: Act, dy) -> torch.Tensor:
+        """Per-channel (sum dy, sum dy*a) -> the BatchNorm's weight / bias gradients and k[3][Cs], the coefficients of dpre."""
+        bn, a = self.bn, out.t
+        npix, cos = out.npix, out.Cs
+        sp = _sp(a)
+        if out.bstats is not None:
+            part, rows, stride, off = out.bstats
+            part_ptr = part.view(-1)[off:]
+        else:
+            rows = L.load().amx_rows_for(npix)
+            part = _empty((rows, 2, cos), a)
+            L.call("amx_bn_bwd_reduce", L.ptr(dy), L.ptr(a), npix, cos, L.ptr(part), sp)
+            part_ptr, stride = part, cos
+        dgamma, dbeta = grad_buffer(bn.weight, a), grad_buffer(bn.bias, a)
+        k = _empty((3, cos), a)
+        L.call("amx_bn_bwd_finalize", L.ptr(part_ptr), rows, stride, cos, self.cout, npix,
+               L.ptr(bn.weight.detach()), L.ptr(self.save_mean), L.ptr(self.save_invstd),
+               L.ptr(dgamma), L.ptr(dbeta), L.ptr(k[0]), L.ptr(k[1]), L.ptr(k[2]), sp)
+        tape.add_param_grad(bn.weight, dgamma)
+        tape.add_param_grad(bn.bias, dbeta)
+        return k
+
+    def _materialise_dpre(self, tape, out: Act, dy, k) -> torch.Tensor:
+        """dpre written to HBM once (amx_bn_bwd_apply; k is None without a BatchNorm), the dropout mask and a
+        DilatedBlock's extra gradient folded in; the convolution's bias gradient is complete when this returns."""
+        a = out.t
+        npix, cos = out.npix, out.Cs
+        sp = _sp(a)
+        bias = self.conv.bias
+        # without dropout the apply pass emits the per-block column sums of dpre it writes; with it they must follow the mask
+        bias_part = _empty((L.load().amx_rows_for(npix), cos), a) if (bias is not None and self.mask is None) else None
+        dpre = _empty(a.shape, a)
+        kk = (L.ptr(k[0]), L.ptr(k[1]), L.ptr(k[2])) if k is not None else (None, None, None)
+        L.call("amx_bn_bwd_apply", L.ptr(dy), L.ptr(a), L.ptr(out.gx), *kk, self.slope, npix, cos,
+               L.ptr(dpre), L.ptr(bias_part), sp)
+        rows = bias_part.shape[0] if bias_part is not None else 0
+        if self.mask is not None:
+            # d conv = mask * lrelu'(.) * (...): the saved activation is already masked, so the sign test of
+            # bn_bwd_apply is right wherever the mask is non-zero, and the mask zeroes the rest
+            L.call("amx_dropout_bwd", L.ptr(dpre), L.ptr(self.mask), dpre.numel(), sp)
+            if out.gx is not None:        # DilatedBlock: the convolution output itself is a summed sub-layer too
+                L.call("amx_add_inplace", L.ptr(dpre), L.ptr(out.gx), dpre.numel(), sp)
+            if bias is not None:                          # bias gradient = column sums of the masked dpre
+                bias_part, rows = _reduce_chunks(dpre, npix, cos, 128 if npix >= 1024 else 1)
+        if bias_part is not None:
+            db = grad_buffer(bias, a)
+            L.call("amx_reduce_rows", L.ptr(bias_part), rows, cos, self.cout, 1.0, L.ptr(db), sp)
+            tape.add_param_grad(bias, db)
+        return dpre
+
+    def _dgrad_plan(self, out: Act) -> str:
+        """How this layer's data gradient is launched (pure: decided once per backward, read by _dpre_on_load and
+        _dgrad).  The wave-specialised kernel forms the layer's BatchNorm / LeakyReLU backward in its loader (round 4), so
+        it must write fresh gradients (no accumulation into an existing one) and nothing else may be folded into dpre
+        (dropout mask, DilatedBlock sum)."""
+        s0, s1 = _two_sources(self.srcs)[:2]
         if not (s0.needs_grad or (s1 is not None and s1.needs_grad)):
-            return False
+            return DGRAD_NONE
+        if self.bn is None or self.mask is not None or out.gx is not None or self.post_slope != 1.0:
+            return DGRAD_GENERAL
         for s in (s0, s1):
             if s is not None and (not s.needs_grad or s.grad is not None or s.gx is not None):
-                return False
+                return DGRAD_GENERAL
         lib = L.load()
-        self._dgrad_split = False
         if lib.amx_conv2d_dgrad_fused_supported(out.Cs, s0.Cs, s1.Cs if s1 else 0, s0.N, s0.H, s0.W, self.taps, self.dil):
-            return True
+            return DGRAD_WS
         # Round 6: a layer that read a CONCATENATION of two sources the kernel takes one at a time (U-Net c5.0: 32 -> 32 + 32)
         # runs its data gradient as TWO launches, one per source, each on the weight image of its half of the input
         # channels — the layer's amx_bn_bwd_apply pass goes, as for the single-launch classes
         if (s1 is not None and DGRAD_SPLIT and s0.C == s0.Cs and s1.C == s1.Cs
                 and lib.amx_conv2d_dgrad_fused_supported(out.Cs, s0.Cs, 0, s0.N, s0.H, s0.W, self.taps, self.dil)
                 and lib.amx_conv2d_dgrad_fused_supported(out.Cs, s1.Cs, 0, s0.N, s0.H, s0.W, self.taps, self.dil)):
-            self._dgrad_split = True
-            return True
-        return False
+            return DGRAD_WS_SPLIT
+        return DGRAD_GENERAL
 
-    def _wgrad(self, tape, dpre, aux, kptr, dw, a, want_bias) -> None:
+    def _dpre_on_load(self, out: Act, plan: str) -> bool:
+        """True: dpre never exists in HBM, BOTH consumers form it in their loaders (amx_conv2d_dgrad_fused /
+        amx_conv2d_wgrad_fused) and no amx_bn_bwd_apply pass runs.  False: materialised once."""
+        return plan in (DGRAD_WS, DGRAD_WS_SPLIT)
+
+    def _wgrad(self, tape, out: Act, dpre, aux, kptr, dw, want_bias: bool) -> None:
         w = self.conv.weight
-        cos = self.out.Cs
+        a, cos = out.t, out.Cs
         sp = _sp(a)
         k1, k2, k3 = kptr
-
-        def colsum(part2d, rows, ncols):
-            """[rows][ncols] -> [ncols] in (at most) two deterministic stages."""
-            if rows > 64:
-                nch = 32 if rows < 1024 else 128
-                tmp = _empty((nch, ncols), a)
-                L.call("amx_reduce_rows_chunked", L.ptr(part2d), rows, ncols, nch, L.ptr(tmp), sp)
-                part2d, rows = tmp, -(-rows // -(-rows // nch))
-            out1 = _empty((ncols,), a)
-            L.call("amx_reduce_rows_chunked", L.ptr(part2d), rows, ncols, 1, L.ptr(out1), sp)
-            return out1
-
-        if self.x_plain is not None:
-            x = self.x_plain
-            N, _, H, W = x.shape
-            if aux is not None:
-                if self.out.wg1_parts is not None:
-                    # the pooling backward already formed the three sums the gradient is linear in (PoolNode.backward)
-                    part3, prows = self.out.wg1_parts
-                    self.out.wg1_parts = None
-                    ncols = 30 * cos
-                    if prows > 16:                       # (the combine kernel walks the rows serially: few, fat chunks)
-                        nch = 16
-                        tmp = _empty((nch, ncols), a)
-                        L.call("amx_reduce_rows_chunked", L.ptr(part3), prows, ncols, nch, L.ptr(tmp), sp)
-                        part3, prows = tmp, -(-prows // -(-prows // nch))
-                    tot = _empty((10 * cos,), a)
-                    L.call("amx_conv1_wgrad_combine", L.ptr(part3), prows, cos, L.ptr(k1), L.ptr(k2), L.ptr(k3), L.ptr(tot), sp)
-                else:
-                    part = _empty((self.rows, 10, cos), a)
-                    L.call("amx_conv1_wgrad_fused", L.ptr(x), L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2), L.ptr(k3),
-                           self.slope, L.ptr(part), N, H, W, cos, self.dil, self.rows, self.rows_pix, sp)
-                    tot = colsum(part, self.rows, 10 * cos)
-                L.call("amx_wgrad_reduce", L.ptr(tot), 1, 9, 1, cos, 1, 1, 0, self.cout, L.ptr(dw), sp)
-                if want_bias:
-                    db = grad_buffer(self.conv.bias, a)
-                    db.copy_(tot[9 * cos: 9 * cos + self.cout])
-                    tape.add_param_grad(self.conv.bias, db)
-            else:
-                part = _empty((self.rows, 9, cos), a)
-                L.call("amx_conv1_wgrad", L.ptr(x), L.ptr(dpre), L.ptr(part), N, H, W, cos, self.dil,
-                       self.rows, self.rows_pix, sp)
-                prows = self.rows
-                if prows > 64:           # thousands of per-block rows: chunk sums first (see colsum)
-                    nch = 32 if prows < 1024 else 128
-                    tmp = _empty((nch, 9 * cos), a)
-                    L.call("amx_reduce_rows_chunked", L.ptr(part), prows, 9 * cos, nch, L.ptr(tmp), sp)
-                    part, prows = tmp, -(-prows // -(-prows // nch))
-                L.call("amx_wgrad_reduce", L.ptr(part), prows, 9, 1, cos, 1, 1, 0, self.cout, L.ptr(dw), sp)
-            tape.add_param_grad(w, dw)
-            return
-        s0 = self.srcs[0]
-        s1 = self.srcs[1] if len(self.srcs) > 1 else None
-        N, H, W = s0.N, s0.H, s0.W
-        C0, C0s = s0.C, s0.Cs
-        C1, C1s = (s1.C, s1.Cs) if s1 else (0, 0)
+        s0, s1, N, H, W, C0, C0s, C1, C1s = _two_sources(self.srcs)
         wrows = L.load().amx_conv2d_wgrad_rows(N, H, W, C0s + C1s, self.cout, self.taps, self.dil)
         ci_pad, co_pad = r16(C0s + C1s), r16(self.cout)
         part = _empty((wrows, self.taps, ci_pad, co_pad), a)
@@ -637,19 +587,10 @@ class ConvNode(_Node):
         if want_bias:
             ks = L.load().amx_conv2d_wgrad_ksplit(N, H, W, C0s + C1s, self.cout, self.taps, self.dil)
             bpart = _empty((ks, co_pad), a)
-        ps0, ps1 = s0.post_slope, (s1.post_slope if s1 else 1.0)
-        if ps0 != 1.0 or ps1 != 1.0:
-            L.call("amx_conv2d_wgrad_act", L.ptr(s0.t), L.ptr(s0.scale), L.ptr(s0.shift), ps0, C0s,
-                   L.ptr(s1.t if s1 else None), L.ptr(s1.scale if s1 else None),
-                   L.ptr(s1.shift if s1 else None), ps1, C1s, L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2),
-                   L.ptr(k3), self.slope, cos, L.ptr(part), L.ptr(bpart), N, H, W, self.cout, self.taps,
-                   self.dil, sp)
-        else:
-            L.call("amx_conv2d_wgrad_fused", L.ptr(s0.t), L.ptr(s0.scale), L.ptr(s0.shift), C0s,
-                   L.ptr(s1.t if s1 else None), L.ptr(s1.scale if s1 else None),
-                   L.ptr(s1.shift if s1 else None), C1s, L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2),
-                   L.ptr(k3), self.slope, cos, L.ptr(part), L.ptr(bpart), N, H, W, self.cout, self.taps,
-                   self.dil, sp)
+        act = _has_input_slope(s0, s1)
+        L.call("amx_conv2d_wgrad_act" if act else "amx_conv2d_wgrad_fused", *_src_args(s0, s1, slopes=act),
+               L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2), L.ptr(k3), self.slope, cos, L.ptr(part), L.ptr(bpart),
+               N, H, W, self.cout, self.taps, self.dil, sp)
         if bpart is not None:
             db = grad_buffer(self.conv.bias, a)
             L.call("amx_reduce_rows", L.ptr(bpart), bpart.shape[0], co_pad, self.cout, 1.0, L.ptr(db), sp)
@@ -657,24 +598,18 @@ class ConvNode(_Node):
         if wrows > 8:                    # two-stage: coalesced (1 KB per row and block) chunk sums first;
             #                              the strided 128 B reads of wgrad_reduce are ~10x slower per byte
             nch = 8 if wrows <= 64 else (32 if wrows < 1024 else 128)
-            ncols = self.taps * ci_pad * co_pad
-            part2 = _empty((nch, ncols), a)
-            L.call("amx_reduce_rows_chunked", L.ptr(part), wrows, ncols, nch, L.ptr(part2), sp)
-            part, wrows = part2, -(-wrows // -(-wrows // nch))
+            part, wrows = _reduce_chunks(part, wrows, self.taps * ci_pad * co_pad, nch)
         L.call("amx_wgrad_reduce", L.ptr(part), wrows, self.taps, ci_pad, co_pad, C0, C0s, C1, self.cout,
                L.ptr(dw), sp)
         tape.add_param_grad(w, dw)
 
-    def _dgrad(self, tape, dpre, aux, kptr, s0, s1, N, H, W, C0, C0s, C1, C1s, cos, sp) -> None:
+    def _dgrad(self, tape, plan: str, cos: int, dpre, aux, kptr) -> None:
         # ---- data gradient(s): forward conv of dpre with the flipped / transposed weight image
         w = self.conv.weight
+        sp = _sp(dpre)
         k1, k2, k3 = kptr
-        need0 = s0.needs_grad
-        need1 = bool(s1 and s1.needs_grad)
-        if not (need0 or need1):
-            return
-        split = aux is not None and s1 is not None and getattr(self, "_dgrad_split", False)
-        wpk = None if split else pack_weights(w, C0, C0s, C1, C1s, self.taps, 1)
+        s0, s1, N, H, W, C0, C0s, C1, C1s = _two_sources(self.srcs)
+        wpk = None if plan == DGRAD_WS_SPLIT else pack_weights(w, C0, C0s, C1, C1s, self.taps, 1)
         bsum_src = s1 is None and s0.wants_bsum_from_dgrad(self, tape.training)      # (asked before s0.grad is allocated)
         tgt = []
         for s in (s0, s1):
@@ -693,39 +628,138 @@ class ConvNode(_Node):
             y1 = scratch
         else:
             scratch, y1 = None, tgt[1][0]
-        if aux is not None:
-            # dpre is formed by the loader of the wave-specialised kernel from (dy, a) (_bwd_fusable guarantees support)
-            assert add0 is None and scratch is None
-            if split:
-                for s, off in ((s0, 0), (s1, C0)):
-                    wh = pack_weights_range(w, off, s.C, s.Cs, self.taps, 1)
-                    L.call("amx_conv2d_dgrad_fused", L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2), L.ptr(k3), self.slope,
-                           cos, L.ptr(wh), L.ptr(s.grad), s.Cs, None, 0, N, H, W, self.taps, self.dil, sp)
-                return
-            if s1 is None and bsum_src:
-                # the gradient written here is the whole dy of the source layer: its BatchNorm-backward sums come out of
-                # this kernel's epilogue, amx_bn_bwd_reduce is not launched for it (ConvNode.backward reads s0.bstats)
-                rows = L.load().amx_conv2d_dgrad_bsum_rows(cos, C0s, N, H, W, self.taps, self.dil)
-                if rows > 0:
-                    part = _empty((rows, 2, C0s), s0.t)
-                    L.call("amx_conv2d_dgrad_fused_bsum", L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2), L.ptr(k3),
-                           self.slope, cos, L.ptr(wpk), L.ptr(tgt[0][0]), C0s, N, H, W, self.taps, self.dil, L.ptr(s0.t),
-                           L.ptr(part), sp)
-                    s0.bstats = (part, rows, C0s, 0)
-                    return
-            L.call("amx_conv2d_dgrad_fused", L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2), L.ptr(k3), self.slope, cos,
-                   L.ptr(wpk), L.ptr(tgt[0][0]), C0s, L.ptr(y1), C1s, N, H, W, self.taps, self.dil, sp)
+        if plan == DGRAD_GENERAL:
+            L.call("amx_conv2d_dgrad", L.ptr(dpre), cos, L.ptr(wpk), L.ptr(add0), L.ptr(tgt[0][0]), C0s, L.ptr(y1), C1s,
+                   N, H, W, self.taps, self.dil, sp)
+            if scratch is not None:
+                L.call("amx_add_inplace", L.ptr(tgt[1][0]), L.ptr(scratch), scratch.numel(), sp)
             return
-        L.call("amx_conv2d_dgrad", L.ptr(dpre), cos, L.ptr(wpk), L.ptr(add0), L.ptr(tgt[0][0]), C0s, L.ptr(y1), C1s,
-               N, H, W, self.taps, self.dil, sp)
-        if scratch is not None:
-            L.call("amx_add_inplace", L.ptr(tgt[1][0]), L.ptr(scratch), scratch.numel(), sp)
+        # dpre is formed by the loader of the wave-specialised kernel from (dy, a) (_dgrad_plan guarantees support)
+        assert add0 is None and scratch is None
+        if plan == DGRAD_WS_SPLIT:
+            for s, off in ((s0, 0), (s1, C0)):
+                wh = pack_weights_range(w, off, s.C, s.Cs, self.taps, 1)
+                L.call("amx_conv2d_dgrad_fused", L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2), L.ptr(k3), self.slope,
+                       cos, L.ptr(wh), L.ptr(s.grad), s.Cs, None, 0, N, H, W, self.taps, self.dil, sp)
+            return
+        if s1 is None and bsum_src:
+            # the gradient written here is the whole dy of the source layer: its BatchNorm-backward sums come out of
+            # this kernel's epilogue, amx_bn_bwd_reduce is not launched for it (ConvNode._bn_bwd_sums reads s0.bstats)
+            rows = L.load().amx_conv2d_dgrad_bsum_rows(cos, C0s, N, H, W, self.taps, self.dil)
+            if rows > 0:
+                part = _empty((rows, 2, C0s), s0.t)
+                L.call("amx_conv2d_dgrad_fused_bsum", L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2), L.ptr(k3),
+                       self.slope, cos, L.ptr(wpk), L.ptr(tgt[0][0]), C0s, N, H, W, self.taps, self.dil, L.ptr(s0.t),
+                       L.ptr(part), sp)
+                s0.bstats = (part, rows, C0s, 0)
+                return
+        L.call("amx_conv2d_dgrad_fused", L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2), L.ptr(k3), self.slope, cos,
+               L.ptr(wpk), L.ptr(tgt[0][0]), C0s, L.ptr(y1), C1s, N, H, W, self.taps, self.dil, sp)
 
 
-# UpsampleBlock forward in one pass (csrc/upconv.hip): AMX_FUSE_UPCONV=0 keeps the two launches (host-side switch, read once)
-FUSE_UPCONV = _os.environ.get("AMX_FUSE_UPCONV", "1") != "0"
-UPCONV_MIN_PIXELS = 1 << 19      # low-res pixels of the launch from which the one-pass kernel wins (profiles/r05_logs/r05_upconv_ab4.log:
-#                                  x16 512^2 949 -> 731 us, x32 256^2 253 -> 170, x32 128^2 122 -> 108; x32 64^2 69 vs 73: two kernels)
+class FirstConvNode(ConvNode):
+    """The net's first layer: (N,1,H,W) input read in place by the VALU kernels of conv1.hip, no data gradient."""
+
+    def __init__(self, tape, x_plain: torch.Tensor, conv, bn, slope: float, drop_p: float = 0.0,
+                 pool_next: bool = False):
+        self.x_plain = x_plain                        # (N,1,H,W) tensor for the Cin==1 kernel
+        self.pool_next = pool_next                    # the output goes straight into a 2x2 max-pool
+        self.pooled = None
+        super().__init__(tape, [], conv, bn, slope, drop_p=drop_p)
+        # training (3x3, BatchNorm, no dropout mask): the consumer's pooling backward may fuse this layer's weight gradient
+        # (PoolNode.backward, amx_pool2x2_bwd_wgrad1); it takes the offer only for a dilation that kernel supports
+        if (FUSE_POOL_WGRAD1 and self.bn is not None and tape.training and tape.need_grad and self.mask is None
+                and self.post_slope == 1.0 and self.taps == 9 and x_plain.shape[1] == 1 and bwd_fuse_enabled()
+                and bool(FUSE & 2)):
+            self.out.wg1 = (x_plain, float(self.slope), self.dil)
+
+    def _forward(self, tape) -> Act:
+        act = super()._forward(tape)
+        if self.pooled is not None:
+            act.pooled = Act(self.pooled, self.cout, needs_grad=False)
+        return act
+
+    def _conv_fwd(self, tape, want_stats: bool):
+        w, b = self.conv.weight, self.conv.bias
+        cos, cop = r4(self.cout), r16(self.cout)
+        x = self.x_plain
+        N, _, H, W = x.shape
+        y = _empty((N, H, W, cos), x)
+        npix = N * H * W
+        self.rows = L.load().amx_rows_for(npix)
+        self.rows_pix = L.load().amx_rows_pix(npix)
+        stats = _empty((self.rows, 2, cop), x) if want_stats else None
+        norm = tape.input_norm if tape.input_norm is not None else (0.0, 1.0)
+        tape.input_norm_used = tape.input_norm is not None
+        if (self.pool_next and FUSE_POOL and self.bn is not None and not tape.training and not tape.need_grad
+                and self.drop_p == 0.0 and L.load().amx_conv1_fwd_pool_supported(H, W, self.dil, self.rows_pix)):
+            # eval mode: the 2x2 max-pool of the normalised output comes out of the same kernel (fcnn.py:123, 219)
+            psc, psh = bn_eval_affine(self.bn, self.cout, cos, y)
+            self.pooled = _empty((N, H // 2, W // 2, cos), x)
+            L.call("amx_conv1_fwd_pool", L.ptr(x), L.ptr(w.detach()), L.ptr(b.detach() if b is not None else None),
+                   L.ptr(y), L.ptr(self.pooled), L.ptr(psc), L.ptr(psh), N, H, W, self.cout, cos, self.dil,
+                   self.slope, self.rows, self.rows_pix, float(norm[0]), float(norm[1]), _sp(x))
+        else:
+            L.call("amx_conv1_fwd", L.ptr(x), L.ptr(w.detach()), L.ptr(b.detach() if b is not None else None),
+                   L.ptr(y), L.ptr(stats), N, H, W, self.cout, cos, self.dil, self.slope, self.rows,
+                   self.rows_pix, float(norm[0]), float(norm[1]), _sp(x))
+        return y, stats, 1, 0
+
+    def _dgrad_plan(self, out: Act) -> str:
+        return DGRAD_NONE
+
+    def _dpre_on_load(self, out: Act, plan: str) -> bool:
+        # no data gradient: the BatchNorm backward is only read by the first-layer weight-gradient kernel, which forms
+        # it while loading (amx_conv1_wgrad_fused) — the 512^2 x 16-channel apply pass of U-Net's c1 (0.32 ms at the very
+        # end of the backward pass, nothing left to overlap it) is not launched at all
+        return (self.bn is not None and self.mask is None and out.gx is None and self.post_slope == 1.0
+                and bwd_fuse_enabled())
+
+    def _wgrad_on_main(self) -> bool:
+        # The net's first layer is the LAST node of backward: nothing follows on the main stream, while the side stream
+        # still drains its backlog of weight gradients — this one runs on the (idle) main stream beside them (round 6:
+        # the step used to end with conv1_wgrad queued behind c2.0's weight gradient, profiles/r06_step_timeline_final.txt)
+        return FIRST_WGRAD_MAIN
+
+    def _wgrad(self, tape, out: Act, dpre, aux, kptr, dw, want_bias: bool) -> None:
+        x = self.x_plain
+        N, _, H, W = x.shape
+        a, cos = out.t, out.Cs
+        sp = _sp(a)
+        k1, k2, k3 = kptr
+        if aux is None:
+            part = _empty((self.rows, 9, cos), a)
+            L.call("amx_conv1_wgrad", L.ptr(x), L.ptr(dpre), L.ptr(part), N, H, W, cos, self.dil,
+                   self.rows, self.rows_pix, sp)
+            prows = self.rows
+            if prows > 64:               # thousands of per-block rows: chunk sums first
+                part, prows = _reduce_chunks(part, prows, 9 * cos, 32 if prows < 1024 else 128)
+            L.call("amx_wgrad_reduce", L.ptr(part), prows, 9, 1, cos, 1, 1, 0, self.cout, L.ptr(dw), sp)
+            tape.add_param_grad(self.conv.weight, dw)
+            return
+        # tot[10][cos]: the nine taps and the bias row, summed over every block
+        tot = _empty((10 * cos,), a)
+        if out.wg1_parts is not None:
+            # the pooling backward already formed the three sums the gradient is linear in (PoolNode.backward)
+            part3, prows = out.wg1_parts
+            out.wg1_parts = None
+            if prows > 16:                       # (the combine kernel walks the rows serially: few, fat chunks)
+                part3, prows = _reduce_chunks(part3, prows, 30 * cos, 16)
+            L.call("amx_conv1_wgrad_combine", L.ptr(part3), prows, cos, L.ptr(k1), L.ptr(k2), L.ptr(k3), L.ptr(tot), sp)
+        else:
+            part = _empty((self.rows, 10, cos), a)
+            L.call("amx_conv1_wgrad_fused", L.ptr(x), L.ptr(dpre), L.ptr(aux), L.ptr(k1), L.ptr(k2), L.ptr(k3),
+                   self.slope, L.ptr(part), N, H, W, cos, self.dil, self.rows, self.rows_pix, sp)
+            prows = self.rows
+            if prows > 64:
+                part, prows = _reduce_chunks(part, prows, 10 * cos, 32 if prows < 1024 else 128)
+            L.call("amx_reduce_rows_chunked", L.ptr(part), prows, 10 * cos, 1, L.ptr(tot), sp)
+        L.call("amx_wgrad_reduce", L.ptr(tot), 1, 9, 1, cos, 1, 1, 0, self.cout, L.ptr(dw), sp)
+        if want_bias:
+            db = grad_buffer(self.conv.bias, a)
+            db.copy_(tot[9 * cos: 9 * cos + self.cout])
+            tape.add_param_grad(self.conv.bias, db)
+        tape.add_param_grad(self.conv.weight, dw)
 
 
 def upconv_fusable(src: "Act", conv) -> bool:
@@ -765,18 +799,13 @@ class UpConvNode(ConvNode):
         if g is None:
             return
         s0 = self.srcs[0]
-        # the stand-in below carries a GRADIENT where ConvNode.backward expects an activation: safe only because a linear
+        # the stand-in below carries a GRADIENT where ConvNode._backward expects an activation: safe only because a linear
         # convolution (no BatchNorm, no LeakyReLU, no dropout) never reads its own output in backward
         assert self.bn is None and self.slope == 1.0 and self.post_slope == 1.0 and self.mask is None
         dv = _empty((s0.N, s0.H, s0.W, hi.Cs), g)
         L.call("amx_upsample2x_bwd", L.ptr(g), L.ptr(dv), s0.N, s0.H, s0.W, hi.Cs, self.up_mode, _sp(g))
         lo = Act(dv, self.cout, needs_grad=True)             # the low-resolution convolution output's stand-in: only its
-        lo.grad = dv                                          # gradient exists (the tensor itself never did)
-        self.out = lo
-        try:
-            super().backward(tape)
-        finally:
-            self.out = hi
+        self._backward(tape, lo, dv)                          # gradient exists (the tensor itself never did)
 
 
 class ResOutNode(_Node):
@@ -803,7 +832,7 @@ class ResOutNode(_Node):
         # the convolution branch gets its own copy when its producer forwards the gradient tensor unchanged to a
         # weight-gradient kernel on the side stream (no BatchNorm in between) while the residual branch keeps
         # accumulating into it.  With a BatchNorm in between the same hazard exists whenever the producer's backward is
-        # formed inside its consumers' loaders (ConvNode._bwd_fusable): the side stream's weight-gradient kernel then
+        # formed inside its consumers' loaders (ConvNode._dpre_on_load): the side stream's weight-gradient kernel then
         # reads THIS tensor as `dy` while the residual branch's data gradient adds into it on the main stream.
         alias_unsafe = (not t.producer) or bwd_fuse_enabled()
         ds2 = _empty(g.shape, g) if (alias_unsafe and r.needs_grad) else None
@@ -833,9 +862,9 @@ class PoolNode(_Node):
             return
         skip = s.grad
         if (s.wg1 is not None and s.gx is None and s.wants_bstats(self, tape.training)
-                and L.load().amx_pool2x2_bwd_wgrad1_supported(s.H, s.W, s.Cs, 1)):
+                and L.load().amx_pool2x2_bwd_wgrad1_supported(s.H, s.W, s.Cs, s.wg1[2])):
             # first layer of the net: its weight-gradient sums come out of this pass, dy itself is not written (see the kernel)
-            x_plain, slope = s.wg1
+            x_plain, slope, _ = s.wg1
             rows = L.load().amx_pool2x2_bwd_rows(s.N, s.H, s.W, s.Cs)
             bstats = _empty((rows, 2, s.Cs), g)
             part3 = _empty((rows, 3, 10, s.Cs), g)
@@ -995,13 +1024,6 @@ class OutputNode(_Node):
         tape.accumulate(s, g)
 
 
-# experiment switch for the eval-mode epilogue fusions (classification head, DilatedBlock sum); 0 = separate kernels
-FUSE_HEAD = _os.environ.get("AMX_FUSE_HEAD", "1") != "0"
-# Eval mode: the 2x2 max-pool that follows a one-layer first block (Unet / dilnet c1) is produced by the first-layer kernel
-# (amx_conv1_fwd_pool); AMX_FUSE_POOL=0 keeps the separate amx_pool2x2_fwd launch (A/B switch, tools/gpu_step_ab.py).
-FUSE_POOL = _os.environ.get("AMX_FUSE_POOL", "1") != "0"
-
-
 def head_fusable(tape, srcs: Sequence[Act], conv, px) -> bool:
     """Can `px` (the net's final 1x1 convolution) be evaluated in the epilogue of `conv` (its last 3x3 layer)?  Eval
     mode only (in training the layer's BatchNorm statistics do not exist before the layer has been computed)."""
@@ -1021,11 +1043,7 @@ class HeadNode(_Node):
     reaches HBM."""
 
     def __init__(self, tape, srcs: Sequence[Act], conv, bn, slope: float, px, mode: int):
-        s0 = srcs[0]
-        s1 = srcs[1] if len(srcs) > 1 else None
-        N, H, W = s0.N, s0.H, s0.W
-        C0, C0s = s0.C, s0.Cs
-        C1, C1s = (s1.C, s1.Cs) if s1 else (0, 0)
+        s0, s1, N, H, W, C0, C0s, C1, C1s = _two_sources(srcs)
         w, b = conv.weight, conv.bias
         cout, K = w.shape[0], px.weight.shape[0]
         cos, cop = r4(cout), r16(cout)
@@ -1047,9 +1065,7 @@ class HeadNode(_Node):
         hw, hb = cached_eval(px, deps, ("head", id(bn), cop, s0.t.device.index), fold)
         shape = (N, K, H, W) if mode == 0 else (N, H, W, K)
         self.value = _empty(shape, s0.t)
-        L.call("amx_conv2d_fwd_head", L.ptr(s0.t), L.ptr(s0.scale), L.ptr(s0.shift), C0s,
-               L.ptr(s1.t if s1 else None), L.ptr(s1.scale if s1 else None), L.ptr(s1.shift if s1 else None), C1s,
-               L.ptr(wpk), L.ptr(b.detach() if b is not None else None), L.ptr(hw), L.ptr(hb), L.ptr(self.value),
+        L.call("amx_conv2d_fwd_head", *_src_args(s0, s1), L.ptr(wpk), L.ptr(b.detach() if b is not None else None), L.ptr(hw), L.ptr(hb), L.ptr(self.value),
                K, mode, N, H, W, cout, float(slope), _sp(s0.t))
         self.grad_out = None
 
@@ -1243,9 +1259,6 @@ def px_loss_fusable(src: Act, conv, target, kind: str = "ce") -> bool:
     return kind in ("ce", "focal") and bool(L.load().amx_px_ce_train_supported(src.Cs, K))
 
 
-FUSE_PX_LOSS = _os.environ.get("AMX_FUSE_PX_LOSS", "1") != "0"
-
-
 # ====================================================================================== tape
 _SIDE_STREAMS: Dict[tuple, "torch.cuda.Stream"] = {}
 
@@ -1341,8 +1354,8 @@ class Tape:
 
     def conv_first(self, x_plain: torch.Tensor, conv, bn=None, slope: float = 1.0, drop_p: float = 0.0,
                    pool_next: bool = False) -> Act:
-        return self._push(ConvNode(self, [], conv, bn, slope, x_plain=x_plain.detach().contiguous(),
-                                   drop_p=drop_p, pool_next=pool_next)).out
+        return self._push(FirstConvNode(self, x_plain.detach().contiguous(), conv, bn, slope, drop_p=drop_p,
+                                        pool_next=pool_next)).out
 
     def pool(self, src: Act) -> Act:
         return self._push(PoolNode(self, src)).out

@@ -976,3 +976,40 @@ def check_pool_backward_with_first_layer_wgrad(device, models=(("Unet", 3, 4), (
         gmax = max(float(g.abs().max()) for g in grads[0])
         for (name, _), a, b in zip(net.named_parameters(), grads[1], grads[0]):
             assert float((a - b).abs().max()) < 2e-5 * gmax, (model, name, float((a - b).abs().max()), gmax)
+
+
+def check_dilated_first_layer_keeps_its_own_wgrad(device):
+    """A DILATED first layer in front of a pool: amx_pool2x2_bwd_wgrad1 forms the sums of a dilation-1 layer only, so the
+    pooling backward must leave the weight gradient to the first-layer kernel.  FUSE_POOL_WGRAD1 on and off then take the
+    same launches: the layer's three parameter gradients are bit-identical."""
+    import torch.nn as nn
+    import atomai_amd.engine as eng
+    from atomai_amd import _lib as L
+    torch.manual_seed(3)
+    conv = nn.Conv2d(1, 4, 3, padding=2, dilation=2).to(device)
+    bn = nn.BatchNorm2d(4).to(device)
+    x = torch.randn(2, 1, 8, 8, device=device)
+    gy = torch.randn(2, 4, 4, 4, device=device)
+    grads, calls = [], []
+    orig = L.call
+    for on in (True, False):
+        eng.FUSE_POOL_WGRAD1 = on
+        seen = []
+
+        def spy(name, *a, _seen=seen):
+            _seen.append(name)
+            return orig(name, *a)
+        L.call = eng.L.call = spy
+        try:
+            tape = eng.Tape(True, True)
+            o = tape.output(tape.pool(tape.conv_first(x, conv, bn, 0.01)))
+            o.grad_out = gy
+            tape.backward()
+        finally:
+            L.call = eng.L.call = orig
+            eng.FUSE_POOL_WGRAD1 = True
+        grads.append([tape.param_grads[id(p)][1].clone() for p in (conv.weight, bn.weight, bn.bias)])
+        calls.append(seen)
+    assert "amx_pool2x2_bwd_wgrad1" not in calls[0] and "amx_pool2x2_bwd_wgrad1" not in calls[1], calls
+    for a, b, nm in zip(grads[0], grads[1], ("conv.weight", "bn.weight", "bn.bias")):
+        assert torch.equal(a, b), (nm, float((a - b).abs().max()))

@@ -540,3 +540,4 @@ def test_head_and_loss_of_the_training_step_in_one_pass():
 
 def test_pool_backward_fused_with_the_first_layer_weight_gradient():
     C.check_pool_backward_with_first_layer_wgrad("cuda")
+    C.check_dilated_first_layer_keeps_its_own_wgrad("cuda")
