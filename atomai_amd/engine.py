@@ -339,8 +339,17 @@ class ConvNode(_Node):
             assert self.slope == 1.0
             self.slope, self.post_slope = self.post_slope, 1.0
         assert self.post_slope == 1.0 or self.slope == 1.0, "one activation per layer"
+        self.cout = conv.weight.shape[0]
+        self._geometry(conv)
+        for src in self.srcs:
+            src.consumed_by(self)
+        self.out = self._forward(tape)
+        self.out.post_slope = self.post_slope
+        self.out.producer = self.bn is not None and self.post_slope == 1.0
+
+    def _geometry(self, conv) -> None:
+        """Sets (taps, dil) and refuses every kernel geometry the launches do not take."""
         w = conv.weight
-        self.cout = w.shape[0]
         self.taps = w.shape[2] * w.shape[3]
         assert self.taps in (1, 9) and w.shape[2] == w.shape[3], "3x3 or 1x1 kernels only"
         self.dil = int(conv.dilation[0]) if self.taps == 9 else 1
@@ -350,11 +359,6 @@ class ConvNode(_Node):
                 "padding must equal dilation ('same' convolution)"
         else:
             assert tuple(conv.padding) == (0, 0)
-        for src in self.srcs:
-            src.consumed_by(self)
-        self.out = self._forward(tape)
-        self.out.post_slope = self.post_slope
-        self.out.producer = self.bn is not None and self.post_slope == 1.0
 
     # -------------------------------------------------------------------------------- forward
     def _forward(self, tape) -> Act:
@@ -762,6 +766,106 @@ class FirstConvNode(ConvNode):
         tape.add_param_grad(self.conv.weight, dw)
 
 
+def pack_weights1d(w: torch.Tensor, cin: int, cin_s: int, taps: int, mode: int) -> torch.Tensor:
+    """MFMA image of an (O, I, taps) Conv1d weight (amx_pack_weights1d: mode 0 forward, 1 data gradient), cached."""
+    def build():
+        n = L.load().amx_pack_weights1d_size(w.shape[0], cin_s, taps)
+        dst = _empty((n,), w)
+        L.call("amx_pack_weights1d", L.ptr(w.detach()), L.ptr(dst), w.shape[0], cin, cin_s, taps, mode, _sp(w))
+        return dst
+    return _pack_cache.get(w, ("1d", cin, cin_s, taps, mode), build)
+
+
+class Conv1dNode(ConvNode):
+    """nn.Conv1d (3 taps with any dilation, or 1 tap) [+bias] [+LeakyReLU] [+BatchNorm1d statistics] over ONE source
+    (csrc/conv1d.hip; atomai/nets/blocks.py:61-76, 300-318 with ndim = 1).  The activation is an ordinary `Act` with
+    H = 1, so the BatchNorm passes, dropout, DilatedSumNode, InputNode / OutputNode and `accumulate` serve unchanged.
+    Backward always reads a materialised dpre (amx_bn_bwd_apply); the data gradient is the forward kernel on the
+    flipped / transposed weight image."""
+
+    def _geometry(self, conv) -> None:
+        w = conv.weight
+        assert w.ndim == 3 and w.shape[2] in (1, 3), "Conv1d kernels of size 3 or 1 only"
+        self.taps = int(w.shape[2])
+        self.dil = int(conv.dilation[0]) if self.taps == 3 else 1
+        assert tuple(conv.stride) == (1,)
+        if self.taps == 3:
+            assert int(conv.padding[0]) == self.dil, "padding must equal dilation ('same' convolution)"
+        else:
+            assert tuple(conv.padding) == (0,)
+        assert len(self.srcs) == 1 and self.srcs[0].H == 1, "a 1-D layer reads one (N, 1, L, C) activation"
+
+    def _conv_fwd(self, tape, want_stats: bool):
+        w, b = self.conv.weight, self.conv.bias
+        cos, cop = r4(self.cout), r16(self.cout)
+        s0 = self.srcs[0]
+        N, Ln = s0.N, s0.W
+        assert w.shape[1] == s0.C, "channel mismatch between conv weight and its source"
+        self._check_launches(tape, s0, Ln, cos)
+        wpk = pack_weights1d(w, s0.C, s0.Cs, self.taps, 0)
+        y = _empty((N, 1, Ln, cos), s0.t)
+        npix = N * Ln
+        self.rows = L.load().amx_rows_for(npix)
+        self.rows_pix = L.load().amx_rows_pix(npix)
+        stats = _empty((self.rows, 2, cop), s0.t) if want_stats else None
+        L.call("amx_conv1d_fwd", L.ptr(s0.t), L.ptr(s0.scale), L.ptr(s0.shift), s0.post_slope, s0.Cs, L.ptr(wpk),
+               L.ptr(b.detach() if b is not None else None), L.ptr(y), L.ptr(stats), N, Ln, self.cout, self.taps,
+               self.dil, self.slope, self.rows, self.rows_pix, _sp(y))
+        return y, stats, 1, 0
+
+    def _check_launches(self, tape, s0: Act, Ln: int, cos: int) -> None:
+        """Refuses before any work is done what one of the layer's launches would refuse: the forward, and with
+        gradients the weight gradient (a larger LDS footprint) and the data gradient (the forward kernel with the two
+        channel counts in each other's place)."""
+        lib = L.load()
+        what = None
+        if not lib.amx_conv1d_supported(s0.Cs, self.cout, Ln, self.taps, self.dil):
+            what = "forward"
+        elif tape.need_grad:
+            if not lib.amx_conv1d_wgrad_supported(s0.Cs, self.cout, Ln, self.taps, self.dil):
+                what = "weight gradient"
+            elif s0.needs_grad and not lib.amx_conv1d_supported(cos, s0.C, Ln, self.taps, self.dil):
+                what = "data gradient"
+        if what is not None:
+            raise L.AmxError(f"Conv1d {s0.C} -> {self.cout} channels over L = {Ln}: dilation = {self.dil} is beyond what "
+                             f"the {what} launch stages in 160 KB of LDS (amx_conv1d_supported / _wgrad_supported)")
+
+    def _dgrad_plan(self, out: Act) -> str:
+        return DGRAD_GENERAL if self.srcs[0].needs_grad else DGRAD_NONE
+
+    def _dpre_on_load(self, out: Act, plan: str) -> bool:
+        return False
+
+    def _wgrad(self, tape, out: Act, dpre, aux, kptr, dw, want_bias: bool) -> None:
+        assert aux is None
+        a = out.t
+        sp = _sp(a)
+        s0 = self.srcs[0]
+        N, Ln = s0.N, s0.W
+        wrows = L.load().amx_conv1d_wgrad_rows(N, Ln)
+        ci_pad, co_pad = r16(s0.Cs), r16(self.cout)
+        part = _empty((wrows, self.taps, ci_pad, co_pad), a)
+        bpart = _empty((wrows, co_pad), a) if want_bias else None
+        L.call("amx_conv1d_wgrad", L.ptr(s0.t), L.ptr(s0.scale), L.ptr(s0.shift), s0.post_slope, s0.Cs, L.ptr(dpre),
+               L.ptr(part), L.ptr(bpart), N, Ln, self.cout, self.taps, self.dil, wrows, sp)
+        if bpart is not None:
+            db = grad_buffer(self.conv.bias, a)
+            L.call("amx_reduce_rows", L.ptr(bpart), wrows, co_pad, self.cout, 1.0, L.ptr(db), sp)
+            tape.add_param_grad(self.conv.bias, db)
+        if wrows > 8:
+            part, wrows = _reduce_chunks(part, wrows, self.taps * ci_pad * co_pad, 8 if wrows <= 64 else 32)
+        L.call("amx_wgrad_reduce", L.ptr(part), wrows, self.taps, ci_pad, co_pad, s0.C, s0.Cs, 0, self.cout, L.ptr(dw), sp)
+        tape.add_param_grad(self.conv.weight, dw)
+
+    def _dgrad(self, tape, plan: str, cos: int, dpre, aux, kptr) -> None:
+        s0 = self.srcs[0]
+        wpk = pack_weights1d(self.conv.weight, s0.C, s0.Cs, self.taps, 1)
+        dx = _empty(s0.t.shape, s0.t)
+        L.call("amx_conv1d_fwd", L.ptr(dpre), None, None, 1.0, cos, L.ptr(wpk), None, L.ptr(dx), None, s0.N, s0.W, s0.C,
+               self.taps, self.dil, 1.0, 0, 0, _sp(dpre))
+        tape.accumulate(s0, dx)
+
+
 def upconv_fusable(src: "Act", conv) -> bool:
     """True when UpsampleBlock's 1x1 convolution + x2 interpolation of `src` runs as ONE launch (amx_upconv1x1_fwd):
     a shape the kernel takes (its results are bit-identical to the two-kernel path there) and large enough to pay."""
@@ -888,20 +992,34 @@ class PoolNode(_Node):
 
 
 class UpsampleNode(_Node):
-    def __init__(self, tape, src: Act, mode: str):
-        assert src.scale is None, "upsample expects a materialised (affine-free) activation"
-        self.src, self.mode = src, {"bilinear": 0, "nearest": 1}[mode]
+    """F.interpolate(scale_factor=2) of an activation: over (H, W), or (ndim = 1) along W of an H = 1 activation.
+    Nearest interpolation only copies values, so it commutes with the producer's per-channel BatchNorm affine: the RAW
+    tensor is upsampled and the pending (scale, shift) is carried on to the new activation — no materialising pass
+    between a BatchNorm and the interpolation (SignalDecoder: deconv1 -> x2 -> deconv2, atomai/nets/ed.py:150-154)."""
+
+    def __init__(self, tape, src: Act, mode: str, ndim: int = 2):
+        self.src, self.mode, self.ndim = src, {"bilinear": 0, "nearest": 1}[mode], ndim
+        assert src.scale is None or (self.mode == 1 and src.post_slope == 1.0), \
+            "a bilinear upsample expects a materialised (affine-free) activation"
+        assert ndim == 2 or (self.mode == 1 and src.H == 1), "1-D upsampling is nearest along L"
         src.consumed_by(self)
-        y = _empty((src.N, 2 * src.H, 2 * src.W, src.Cs), src.t)
-        L.call("amx_upsample2x_fwd", L.ptr(src.t), L.ptr(y), src.N, src.H, src.W, src.Cs, self.mode, _sp(y))
-        self.out = Act(y, src.C, needs_grad=src.needs_grad)
+        if ndim == 1:
+            y = _empty((src.N, 1, 2 * src.W, src.Cs), src.t)
+            L.call("amx_upsample1d2x_fwd", L.ptr(src.t), L.ptr(y), src.N, src.W, src.Cs, _sp(y))
+        else:
+            y = _empty((src.N, 2 * src.H, 2 * src.W, src.Cs), src.t)
+            L.call("amx_upsample2x_fwd", L.ptr(src.t), L.ptr(y), src.N, src.H, src.W, src.Cs, self.mode, _sp(y))
+        self.out = Act(y, src.C, src.scale, src.shift, needs_grad=src.needs_grad)
 
     def backward(self, tape) -> None:
         s, g = self.src, self.out.grad
         if g is None or not s.needs_grad:
             return
         dv = _empty(s.t.shape, s.t)
-        L.call("amx_upsample2x_bwd", L.ptr(g), L.ptr(dv), s.N, s.H, s.W, s.Cs, self.mode, _sp(g))
+        if self.ndim == 1:
+            L.call("amx_upsample1d2x_bwd", L.ptr(g), L.ptr(dv), s.N, s.W, s.Cs, _sp(g))
+        else:
+            L.call("amx_upsample2x_bwd", L.ptr(g), L.ptr(dv), s.N, s.H, s.W, s.Cs, self.mode, _sp(g))
         tape.accumulate(s, dv)
 
 
@@ -1346,8 +1464,9 @@ class Tape:
 
     def conv(self, srcs, conv, bn=None, slope: float = 1.0, post_slope: float = 1.0, drop_p: float = 0.0,
              keep_unmasked: bool = False) -> Act:
-        return self._push(ConvNode(self, srcs, conv, bn, slope, post_slope=post_slope, drop_p=drop_p,
-                                   keep_unmasked=keep_unmasked)).out
+        cls = Conv1dNode if isinstance(conv, torch.nn.Conv1d) else ConvNode
+        return self._push(cls(self, srcs, conv, bn, slope, post_slope=post_slope, drop_p=drop_p,
+                              keep_unmasked=keep_unmasked)).out
 
     def res_out(self, t: Act, r: Act, slope: float) -> Act:
         return self._push(ResOutNode(self, t, r, slope)).out
@@ -1362,6 +1481,9 @@ class Tape:
 
     def upsample(self, src: Act, mode: str) -> Act:
         return self._push(UpsampleNode(self, src, mode)).out
+
+    def upsample1d(self, src: Act, mode: str = "nearest") -> Act:
+        return self._push(UpsampleNode(self, src, mode, ndim=1)).out
 
     def upconv(self, src: Act, conv, mode: str) -> Act:
         return self._push(UpConvNode(self, src, conv, mode)).out

@@ -97,6 +97,46 @@ class BCEWithLogitsLoss(nn.Module):
         return "BCEWithLogitsLoss()"
 
 
+class _MSEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        p, t = pred.detach(), target.detach()
+        n = p.numel()
+        need = pred.requires_grad
+        dl = torch.empty_like(p) if need else None
+        rows = L.load().amx_mse_rows(n)
+        part = torch.empty(rows, dtype=torch.float32, device=p.device)
+        sp = L.stream_ptr(p)
+        L.call("amx_mse_fwd_bwd", L.ptr(p), L.ptr(t), L.ptr(dl), L.ptr(part), n, rows, sp)
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        L.call("amx_reduce_rows", L.ptr(part), rows, 1, 1, 1.0 / n, L.ptr(loss), sp)
+        ctx.dl = dl
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dl, ctx.dl = ctx.dl, None
+        return _times_upstream(dl, g), None
+
+
+class MSELoss(nn.MSELoss):
+    """torch.nn.MSELoss whose mean reduction over same-shape contiguous fp32 device tensors is ONE pass that also
+    produces d loss / d prediction (csrc/signal.hip: amx_mse_fwd_bwd, deterministic two-stage sum) — the criterion of the
+    im2spec / spec2im trainers.  Every other call (another reduction, broadcasting shapes, other dtypes, a target that
+    requires a gradient, host tensors) is the parent class's, warnings included."""
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        on_device = input.is_cuda or L.is_test_backend()
+        if (self.reduction == "mean" and on_device and input.device == target.device and input.shape == target.shape
+                and input.dtype == torch.float32 and target.dtype == torch.float32 and input.numel() > 0
+                and input.is_contiguous() and target.is_contiguous() and not target.requires_grad):
+            return _MSEFn.apply(input, target)
+        return super().forward(input, target)
+
+    def __repr__(self):
+        return "MSELoss()"
+
+
 def dice_launch_plan(N: int, K: int, H: int, W: int):
     """(B, rows, nch): bins of the reference's dice loss (2 for one class, else K * W: one per class and image COLUMN,
     losses.py:85), rows of the partial tensor of amx_dice_sums / amx_px_dice_sums, chunk rows handed to amx_dice_finalize."""
@@ -244,7 +284,7 @@ def select_loss(loss: str, nb_classes: int = None, **kwargs):
     if loss == 'ce' and nb_classes > 2:
         return CrossEntropyLoss()
     if loss == 'mse':
-        return torch.nn.MSELoss()
+        return MSELoss()
     if hasattr(loss, "__call__"):
         return loss
     if loss in ('nll', 'multitask_nll', 'multitask_ce'):

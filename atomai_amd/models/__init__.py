@@ -1,8 +1,9 @@
 from .dgm import VAE, BaseVAE, jrVAE, jVAE, rVAE
 from .dklgp import dklGPR
+from .imspec import ImSpec
 from .segmentor import Segmentor
-from .loaders import (load_ensemble, load_model, load_pretrained_model, load_seg_model,  # noqa: E402
-                      load_vae_model)
+from .loaders import (load_ensemble, load_imspec_model, load_model, load_pretrained_model,  # noqa: E402
+                      load_seg_model, load_vae_model)
 
-__all__ = ["Segmentor", "BaseVAE", "VAE", "rVAE", "jVAE", "jrVAE", "dklGPR", "load_model", "load_ensemble", "load_pretrained_model",
-           "load_seg_model", "load_vae_model"]
+__all__ = ["Segmentor", "ImSpec", "BaseVAE", "VAE", "rVAE", "jVAE", "jrVAE", "dklGPR", "load_model", "load_ensemble", "load_pretrained_model",
+           "load_seg_model", "load_imspec_model", "load_vae_model"]

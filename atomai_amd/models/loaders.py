@@ -6,7 +6,7 @@ atomai/trainers/trainer.py:344-358 and atomai/trainers/vitrainer.py:361-377 in t
 written by the reference loads here onto the HIP modules (same state-dict keys / shapes), and files written
 here hold only torch types (the fused optimizer is stored as its ``torch.optim.Adam`` equivalent).
 
-Model families outside SURVEY.md section 8 (imspec / reg / cls / denoising autoencoder) raise.
+Model families outside SURVEY.md section 8 (reg / cls / denoising autoencoder) raise, and so do ImSpec ensembles.
 """
 import warnings
 from copy import deepcopy as dc
@@ -16,9 +16,10 @@ import torch
 
 from ..utils import average_weights
 from .dgm import VAE, BaseVAE, jrVAE, jVAE, rVAE
+from .imspec import ImSpec
 from .segmentor import Segmentor
 
-_OUT_OF_SCOPE = ("imspec", "reg", "cls", "denoising_autoencoder")
+_OUT_OF_SCOPE = ("reg", "cls", "denoising_autoencoder")
 
 
 def _read(filepath: str) -> Dict:
@@ -40,6 +41,8 @@ def load_model(filepath: str) -> Union[Segmentor, BaseVAE, Dict[str, torch.Tenso
             return load_seg_model(loaded)
         if model_type == "vae":
             return load_vae_model(loaded)
+        if model_type == "imspec":
+            return load_imspec_model(loaded)
     if model_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"model type '{model_type}' is outside the MI355X hot path of this build")
     raise ValueError("The model type {} cannot be loaded".format(model_type))
@@ -54,6 +57,26 @@ def load_seg_model(meta_dict: Dict) -> Type[Segmentor]:
     model.net.load_state_dict(weights)
     if "optimizer" in meta_dict:
         model.optimizer = meta_dict.pop("optimizer")
+    model.net.eval()
+    return model
+
+
+def load_imspec_model(meta_dict: Dict) -> Type[ImSpec]:
+    """ImSpec from {in_dim, out_dim, latent_dim, weights, [optimizer], **architecture kwargs}, written here or by the
+    reference.  Deviation: the reference's loader drops its own "batchnorm" entry (atomai/models/loaders.py), so a model
+    trained with batch_norm=False is rebuilt WITH BatchNorm there and its weights fail to load; here the entry is mapped
+    to the ``batch_norm`` argument."""
+    in_dim = meta_dict.pop("in_dim")
+    out_dim = meta_dict.pop("out_dim")
+    latent_dim = meta_dict.pop("latent_dim")
+    weights = meta_dict.pop("weights")
+    if "batchnorm" in meta_dict:
+        meta_dict["batch_norm"] = meta_dict.pop("batchnorm")
+    optimizer = meta_dict.pop("optimizer", None)
+    model = ImSpec(in_dim, out_dim, latent_dim, **meta_dict)
+    model.net.load_state_dict(weights)
+    if optimizer is not None:
+        model.optimizer = optimizer
     model.net.eval()
     return model
 
@@ -92,6 +115,9 @@ def load_ensemble(filepath: str) -> Tuple[Type[torch.nn.Module], Dict[int, Dict[
     loaded["weights"] = average_weights(loaded["weights"])
     if model_type == "seg":
         smodel = load_seg_model(loaded)
+    elif model_type == "imspec":
+        raise NotImplementedError("ImSpec ensembles are outside the MI355X hot path of this build "
+                                  "(single ImSpec models load with load_model)")
     elif model_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"model type '{model_type}' is outside the MI355X hot path of this build")
     else:

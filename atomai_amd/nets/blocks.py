@@ -4,6 +4,10 @@ Same constructor signatures, same module tree (``self.block`` / ``self.conv`` / 
 are nn.Sequential / nn.Conv2d holding nn.Conv2d / nn.LeakyReLU / nn.BatchNorm2d children), hence the
 same ``state_dict()`` keys, shapes and RNG-order initialisation as the reference.  The children are
 parameter containers only: ``forward`` never calls them — it emits HIP kernels through engine.Tape.
+
+``ConvBlock`` and ``DilatedBlock`` also take ``ndim=1`` (the ImSpec family): nn.Conv1d / nn.BatchNorm1d children with
+``(O, I, 3)`` weights, evaluated by csrc/conv1d.hip on ``(N, C, L)`` tensors.  ``UpsampleBlock(ndim=1)`` and
+``ResBlock(ndim=1)`` raise: no model of the reference uses them.
 """
 from typing import List, Sequence, Tuple, Union
 
@@ -18,13 +22,13 @@ def _layers(seq: nn.Sequential):
     """Groups an nn.Sequential [conv, (dropout), lrelu, (bn)]* into (conv, slope, bn, dropout) tuples."""
     out, cur = [], None
     for m in seq:
-        if isinstance(m, (nn.Conv2d,)):
+        if isinstance(m, (nn.Conv2d, nn.Conv1d)):
             if cur:
                 out.append(cur)
             cur = [m, 1.0, None, None]
         elif isinstance(m, nn.LeakyReLU):
             cur[1] = float(m.negative_slope)
-        elif isinstance(m, nn.BatchNorm2d):
+        elif isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d)):
             cur[2] = m
         elif isinstance(m, nn.Dropout):
             cur[3] = m
@@ -40,7 +44,9 @@ def _drop_p(drop) -> float:
 
 
 class _HipBlock(nn.Module):
-    """Common forward: NCHW tensor -> tape -> NCHW tensor (module-boundary behaviour of the reference)."""
+    """Common forward: NCHW tensor -> tape -> NCHW tensor (module-boundary behaviour of the reference).  A 1-D block
+    takes (N, C, L): on the tape it is the (N, C, 1, L) view of the same memory."""
+    ndim = 2
 
     def _emit(self, tape: Tape, srcs: Sequence[Act]) -> Act:
         raise NotImplementedError
@@ -51,13 +57,18 @@ class _HipBlock(nn.Module):
         return node, self._emit(tape, [node.out])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.ndim == 1:
+            if x.ndim != 3:
+                raise AssertionError("expected a (N, C, L) tensor")
+            x = x.unsqueeze(2)
         if x.ndim != 4:
             raise AssertionError("expected a (N, C, H, W) tensor")
 
         def build(tape, xin):
             node, act = self._emit_input(tape, xin)
             return node, tape.output(act)
-        return run_tape(build, x, list(self.parameters()), self.training)
+        y = run_tape(build, x, list(self.parameters()), self.training)
+        return y.squeeze(2) if self.ndim == 1 else y
 
 
 class ConvBlock(_HipBlock):
@@ -70,18 +81,18 @@ class ConvBlock(_HipBlock):
         super().__init__()
         if not 0 < ndim < 3:
             raise AssertionError("ndim must be equal to 1 or 2")
-        if ndim == 1:
-            raise NotImplementedError("1-D ConvBlock (ImSpec family) is outside the MI355X hot path")
+        self.ndim = ndim
+        conv_cls, bn_cls = (nn.Conv2d, nn.BatchNorm2d) if ndim == 2 else (nn.Conv1d, nn.BatchNorm1d)
         block = []
         for idx in range(nb_layers):
             input_channels = output_channels if idx > 0 else input_channels
-            block.append(nn.Conv2d(input_channels, output_channels, kernel_size=kernel_size,
-                                   stride=stride, padding=padding))
+            block.append(conv_cls(input_channels, output_channels, kernel_size=kernel_size,
+                                  stride=stride, padding=padding))
             if dropout_ > 0:
                 block.append(nn.Dropout(dropout_))
             block.append(nn.LeakyReLU(negative_slope=lrelu_a))
             if batch_norm:
-                block.append(nn.BatchNorm2d(output_channels))
+                block.append(bn_cls(output_channels))
         self.block = nn.Sequential(*block)
 
     def _emit(self, tape, srcs, head=None):
@@ -124,7 +135,7 @@ class UpsampleBlock(_HipBlock):
         if not 0 < ndim < 3:
             raise AssertionError("ndim must be equal to 1 or 2")
         if ndim == 1:
-            raise NotImplementedError("1-D UpsampleBlock is outside the MI355X hot path")
+            raise NotImplementedError("1-D UpsampleBlock is outside the MI355X hot path (no model of the reference uses it)")
         if scale_factor != 2:
             raise NotImplementedError("only scale_factor=2 is on the MI355X hot path")
         self.scale_factor = scale_factor
@@ -149,18 +160,18 @@ class DilatedBlock(_HipBlock):
         super().__init__()
         if not 0 < ndim < 3:
             raise AssertionError("ndim must be equal to 1 or 2")
-        if ndim == 1:
-            raise NotImplementedError("1-D DilatedBlock is outside the MI355X hot path")
+        self.ndim = ndim
+        conv_cls, bn_cls = (nn.Conv2d, nn.BatchNorm2d) if ndim == 2 else (nn.Conv1d, nn.BatchNorm1d)
         atrous_module = []
         for idx, (dil, pad) in enumerate(zip(dilation_values, padding_values)):
             input_channels = output_channels if idx > 0 else input_channels
-            atrous_module.append(nn.Conv2d(input_channels, output_channels, kernel_size=kernel_size,
-                                           stride=stride, padding=pad, dilation=dil, bias=True))
+            atrous_module.append(conv_cls(input_channels, output_channels, kernel_size=kernel_size,
+                                          stride=stride, padding=pad, dilation=dil, bias=True))
             if dropout_ > 0:
                 atrous_module.append(nn.Dropout(dropout_))
             atrous_module.append(nn.LeakyReLU(negative_slope=lrelu_a))
             if batch_norm:
-                atrous_module.append(nn.BatchNorm2d(output_channels))
+                atrous_module.append(bn_cls(output_channels))
         self.atrous_module = nn.Sequential(*atrous_module)
 
     def _emit(self, tape, srcs):
@@ -172,7 +183,8 @@ class DilatedBlock(_HipBlock):
         has_drop = any(d is not None for _, _, _, d in layers)
         dropping = has_drop and tape.training and any(_drop_p(d) > 0 for _, _, _, d in layers)
         for i, (conv, slope, bn, drop) in enumerate(layers):
-            if i == len(layers) - 1 and not has_drop and dsum_fusable(tape, srcs, conv, acts):
+            if (i == len(layers) - 1 and not has_drop and self.ndim == 2
+                    and dsum_fusable(tape, srcs, conv, acts)):
                 return tape.conv_dsum(srcs[0], conv, bn, slope, acts)      # eval: the block's sum in this layer's epilogue
             a = tape.conv(srcs, conv, bn, slope, drop_p=_drop_p(drop) if dropping else 0.0, keep_unmasked=dropping)
             acts.append(a)
@@ -192,7 +204,7 @@ class ResBlock(_HipBlock):
         if not 0 < ndim < 3:
             raise AssertionError("ndim must be equal to 1 or 2")
         if ndim == 1:
-            raise NotImplementedError("1-D ResBlock (ImSpec family) is outside the MI355X hot path")
+            raise NotImplementedError("1-D ResBlock is outside the MI355X hot path (no model of the reference uses it)")
         self.lrelu_a = lrelu_a
         self.batch_norm = batch_norm
         self.c0 = nn.Conv2d(input_channels, output_channels, kernel_size=1, stride=1, padding=0)

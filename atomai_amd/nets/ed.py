@@ -1,11 +1,15 @@
-"""VAE encoder / decoder networks (reference: atomai/nets/ed.py:292-343, 530-687, 725-790).
+"""Encoder / decoder networks of the VAEs (reference: atomai/nets/ed.py:292-343, 530-687, 725-790) and of the
+im2spec / spec2im models (``SignalEncoder`` / ``SignalDecoder`` / ``SignalED``, atomai/nets/ed.py:20-228, 690-722).
 
 * ``fcEncoderNet`` / ``fcDecoderNet`` are dense layers on (B x features) matrices: their ``nn.Linear`` children are
   parameter containers only, the arithmetic (GEMM + bias + Tanh, forward and both gradients) runs on the fp32-MFMA
   GEMM of csrc/linear.hip (``nets/_linear.py``).
 * ``rDecoderNet`` — the per-pixel spatial decoder where the step spends its time — runs the fused HIP
   kernels of csrc/rdecoder.hip (all hidden activations stay in LDS, forward and backward).
-Module trees / state-dict keys / RNG-order initialisation are those of the reference.
+* ``SignalEncoder`` / ``SignalDecoder`` run their convolution blocks — 1-D (csrc/conv1d.hip) or 2-D — on the HIP tape and
+  their ``fc`` layers on the MFMA GEMM.
+Module trees / state-dict keys / RNG-order initialisation are those of the reference.  What raises: the 1-D (spectral)
+VAE encoders / decoders, and a 2-D ``SignalDecoder`` with more than 6 layers (dilations above 6).
 """
 from typing import List, Optional, Tuple
 
@@ -418,6 +422,147 @@ class convDecoderNet(nn.Module):
         params = list(self.decoder.parameters()) + list(self.conv_1x1.parameters())
         h = run_tape(build, h0.contiguous(), params, self.training).reshape(-1, *self.out_dim)
         return h.squeeze(1) if h.size(1) == 1 else h.permute(0, 2, 3, 1)
+
+
+def _signal_dims(signal_dim) -> Tuple[int]:
+    if isinstance(signal_dim, int):
+        signal_dim = (signal_dim,)
+    if not 0 < len(signal_dim) < 3:
+        raise AssertionError("signal dimensionality must be to 1D or 2D")
+    return tuple(int(s) for s in signal_dim)
+
+
+def avg_pool(x: torch.Tensor, k: int) -> torch.Tensor:
+    """F.avg_pool1d(x, k, k) / F.avg_pool2d(x, k, k) of the one-channel net input (N, 1, L) / (N, 1, H, W), floor
+    semantics (csrc/signal.hip: amx_avgpool_fwd).  Forward only."""
+    if x.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("the input average pooling (downsampling) has no backward on the HIP path: "
+                                  "pass an input that does not require a gradient")
+    if x.ndim not in (3, 4) or x.shape[1] != 1:
+        raise AssertionError("expected a one-channel (N, 1, L) or (N, 1, H, W) input")
+    x = x.detach().float().contiguous()
+    N, H, W = x.shape[0], (x.shape[2] if x.ndim == 4 else 1), x.shape[-1]
+    kh = k if x.ndim == 4 else 1
+    shape = (N, 1, H // kh, W // k) if x.ndim == 4 else (N, 1, W // k)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    L.call("amx_avgpool_fwd", L.ptr(x), L.ptr(y), N, H, W, kh, k, L.stream_ptr(x))
+    return y
+
+
+class SignalEncoder(nn.Module):
+    """1-D / 2-D signal -> latent vector (reference: atomai/nets/ed.py:20-79): [average pooling by ``downsampling``] ->
+    ConvBlock(ndim, nb_layers, 1 -> nb_filters, LeakyReLU(0.1), batch_norm) on the HIP tape -> flatten in NCHW order ->
+    ``fc`` on the MFMA GEMM."""
+
+    def __init__(self, signal_dim: Tuple[int], z_dim: int, nb_layers: int, nb_filters: int, **kwargs: int) -> None:
+        super().__init__()
+        from .blocks import ConvBlock
+        signal_dim = _signal_dims(signal_dim)
+        ndim = 2 if len(signal_dim) == 2 else 1
+        self.downsample = kwargs.get("downsampling", 0)
+        bn = kwargs.get('batch_norm', True)
+        if self.downsample:
+            signal_dim = [s // self.downsample for s in signal_dim]
+        n = int(np.prod(signal_dim))
+        self.reshape_ = nb_filters * n
+        self.conv = ConvBlock(ndim, nb_layers, 1, nb_filters, lrelu_a=0.1, batch_norm=bn)
+        self.fc = nn.Linear(nb_filters * n, z_dim)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.downsample:
+            x = avg_pool(x, self.downsample)
+        feats = self.conv(x.contiguous()).reshape(-1, self.reshape_)
+        return linear(feats, self.fc.weight, self.fc.bias)
+
+
+class SignalDecoder(nn.Module):
+    """Latent vector -> 1-D / 2-D signal (reference: atomai/nets/ed.py:82-157): ``fc`` on the MFMA GEMM -> reshape ->
+    ONE tape for [deconv1 -> nearest x2 -> deconv2 -> nearest x2] -> DilatedBlock(dilations 1 .. nb_layers) ->
+    ConvBlock(nb_filters -> 1) -> ``out`` (1 x 1).  The two interpolations carry the BatchNorm affine of the block
+    before them (engine.UpsampleNode): no materialising pass inside the chain.  In 2-D the convolution kernels take
+    dilations up to 6, so ``nb_layers`` > 6 raises there; the 1-D kernel has no such limit."""
+
+    def __init__(self, signal_dim: Tuple[int], z_dim: int, nb_layers: int, nb_filters: int, **kwargs: bool) -> None:
+        super().__init__()
+        from .blocks import ConvBlock, DilatedBlock
+        self.upsampling = kwargs.get("upsampling", False)
+        bn = kwargs.get('batch_norm', True)
+        signal_dim = _signal_dims(signal_dim)
+        ndim = 2 if len(signal_dim) == 2 else 1
+        if ndim == 2 and nb_layers > 6:
+            raise NotImplementedError("a 2-D SignalDecoder with more than 6 layers needs dilations above 6, which the 2-D "
+                                      "convolution kernels do not take")
+        self.ndim = ndim
+        if self.upsampling:
+            signal_dim = [s // 4 for s in signal_dim]
+        n = int(np.prod(signal_dim))
+        self.reshape_ = (nb_filters, *signal_dim)
+        self.fc = nn.Linear(z_dim, nb_filters * n)
+        if self.upsampling:
+            self.deconv1 = ConvBlock(ndim, 1, nb_filters, nb_filters, lrelu_a=0.1, batch_norm=bn)
+            self.deconv2 = ConvBlock(ndim, 1, nb_filters, nb_filters, lrelu_a=0.1, batch_norm=bn)
+        dil = list(range(1, nb_layers + 1))
+        self.dilblock = DilatedBlock(ndim, nb_filters, nb_filters, dilation_values=dil, padding_values=dil,
+                                     lrelu_a=0.1, batch_norm=bn)
+        self.conv = ConvBlock(ndim, 1, nb_filters, 1, lrelu_a=0.1, batch_norm=bn)
+        self.out = nn.Conv2d(1, 1, 1) if ndim == 2 else nn.Conv1d(1, 1, 1)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from ._function import run_tape
+        h0 = linear(x, self.fc.weight, self.fc.bias).reshape(-1, *self.reshape_)
+        if self.ndim == 1:
+            h0 = h0.unsqueeze(2)                                  # (B, F, 1, L): the tape's view of a 1-D signal
+
+        def up(tape, act):
+            return tape.upsample(act, "nearest") if self.ndim == 2 else tape.upsample1d(act, "nearest")
+
+        def build(tape, xin):
+            node = tape.input(xin)
+            act = node.out
+            if self.upsampling:
+                act = up(tape, self.deconv1._emit(tape, [act]))
+                act = up(tape, self.deconv2._emit(tape, [act]))
+            act = self.dilblock._emit(tape, [act])
+            act = self.conv._emit(tape, [act])
+            return node, tape.output(tape.conv([act], self.out, None, 1.0))
+        params = [p for n, p in self.named_parameters() if not n.startswith("fc.")]
+        y = run_tape(build, h0.contiguous(), params, self.training)
+        return y.squeeze(2) if self.ndim == 1 else y
+
+
+class SignalED(nn.Module):
+    """im2spec / spec2im: SignalEncoder(feature_dim) -> latent vector -> SignalDecoder(target_dim)
+    (reference: atomai/nets/ed.py:160-228; same arguments and defaults)."""
+
+    def __init__(self, feature_dim: Tuple[int], target_dim: Tuple[int], latent_dim: int, nblayers_encoder: int = 2,
+                 nblayers_decoder: int = 2, nbfilters_encoder: int = 64, nbfilters_decoder: int = 2,
+                 batch_norm: bool = True, encoder_downsampling: int = 0, decoder_upsampling: bool = False) -> None:
+        super().__init__()
+        self.encoder = SignalEncoder(feature_dim, latent_dim, nblayers_encoder, nbfilters_encoder,
+                                     batch_norm=batch_norm, downsampling=encoder_downsampling)
+        self.decoder = SignalDecoder(target_dim, latent_dim, nblayers_decoder, nbfilters_decoder,
+                                     batch_norm=batch_norm, upsampling=decoder_upsampling)
+
+    def encode(self, features: torch.Tensor) -> torch.Tensor:
+        return self.encoder(features)
+
+    def decode(self, latent: torch.Tensor) -> torch.Tensor:
+        return self.decoder(latent)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.decode(self.encode(x))
+
+
+def init_imspec_model(in_dim: Tuple[int], out_dim: Tuple[int], latent_dim: int, **kwargs):
+    """SignalED + metadict with the reference's keys and defaults (ed.py:690-722; the BatchNorm switch is stored under
+    "batchnorm", as there)."""
+    keys = (("nblayers_encoder", 3), ("nblayers_decoder", 4), ("nbfilters_encoder", 64), ("nbfilters_decoder", 64),
+            ("batch_norm", True), ("encoder_downsampling", 0), ("decoder_upsampling", False))
+    arch = {k: kwargs.get(k, d) for k, d in keys}
+    net = SignalED(in_dim, out_dim, latent_dim, **arch)
+    meta_state_dict = {"model_type": "imspec", "in_dim": in_dim, "out_dim": out_dim, "latent_dim": latent_dim}
+    meta_state_dict.update({("batchnorm" if k == "batch_norm" else k): v for k, v in arch.items()})
+    return net, meta_state_dict
 
 
 def init_VAE_nets(in_dim: Tuple[int], latent_dim: int, coord: int = 0, discrete_dim: Optional[List] = None,

@@ -1,5 +1,5 @@
 from .epredictor import EnsemblePredictor, ensemble_locate
 from .locator import Locator
-from .predictor import BasePredictor, SegPredictor
+from .predictor import BasePredictor, ImSpecPredictor, SegPredictor
 
-__all__ = ["BasePredictor", "SegPredictor", "Locator", "EnsemblePredictor", "ensemble_locate"]
+__all__ = ["BasePredictor", "SegPredictor", "ImSpecPredictor", "Locator", "EnsemblePredictor", "ensemble_locate"]

@@ -23,7 +23,8 @@ class EnsemblePredictor(BasePredictor):
         if output_type not in ["image", "spectra"]:
             raise TypeError("Supported output types are 'image' and 'spectra'")
         if data_type != "image" or output_type != "image":
-            raise NotImplementedError("spectra (ImSpec) ensembles are outside the MI355X hot path of this build")
+            raise NotImplementedError("ensembles of ImSpec models (spectra in or out) are outside the MI355X hot path of "
+                                      "this build (single models: aoi.models.ImSpec / predictors.ImSpecPredictor)")
         self.device = "cpu"
         if kwargs.get("use_gpu", True) and torch.cuda.is_available():
             self.device = kwargs.get("device") or "cuda"

@@ -1,4 +1,4 @@
-"""BasePredictor / SegPredictor (reference: atomai/predictors/predictor.py:23-298).
+"""BasePredictor / SegPredictor / ImSpecPredictor (reference: atomai/predictors/predictor.py:23-395).
 
 Same constructor arguments and numpy-in / numpy-out behaviour.  The frame loop of the reference (one
 frame per launch, synchronous H2D/D2H, host ``torch.zeros`` of the whole output) is replaced by a
@@ -17,7 +17,8 @@ import torch
 from ..nets.fcnn import _HipNet, predict_proba
 from .locator import Locator, locate_device
 from .. import _lib as L
-from ..utils import get_downsample_factor, get_nb_classes, img_pad, img_resize, set_train_rng, torch_format_image
+from ..utils import (get_downsample_factor, get_nb_classes, img_pad, img_resize, set_train_rng, torch_format_image,
+                     torch_format_spectra)
 
 
 class BasePredictor:
@@ -436,3 +437,44 @@ class SegPredictor(BasePredictor):
             print("\n" + str(decoded.shape[0]) + word + "decoded in approximately "
                   + str(np.around(time.time() - start_time, decimals=4)) + " seconds")
         return decoded, coordinates
+
+
+class ImSpecPredictor(BasePredictor):
+    """Prediction with a trained im2spec / spec2im model (predictor.py:301-395): ``output_dim`` is (length,) for
+    image -> spectrum and (height, width) for spectrum -> image; numpy in, numpy out.  The batches go through
+    BasePredictor.batch_predict, i.e. the eval-mode HIP tape of ``SignalED``."""
+
+    def __init__(self, trained_model: Type[torch.nn.Module], output_dim: Tuple[int], use_gpu: bool = False,
+                 **kwargs: str) -> None:
+        super().__init__(trained_model, use_gpu)
+        if isinstance(output_dim, int):
+            output_dim = (output_dim,)
+        if len(output_dim) not in [1, 2]:
+            raise ValueError("output_dim must be a two-value tuple for images and a single-value tuple for spectra")
+        set_train_rng(1)
+        self.output_dim = output_dim
+        self.verbose = kwargs.get("verbose", True)
+
+    def preprocess(self, signal: np.ndarray, norm: bool = True) -> torch.Tensor:
+        """A single image / spectrum gets its batch axis; then (n, 1, ...) float32, min-max normalised over the whole
+        stack when ``norm``."""
+        if len(self.output_dim) == 1:
+            return torch_format_image(signal[None] if signal.ndim == 2 else signal, norm)
+        return torch_format_spectra(signal[None] if signal.ndim == 1 else signal, norm)
+
+    def predict(self, signal: np.ndarray, **kwargs: int) -> np.ndarray:
+        """``num_batches`` (default 10), ``norm`` (default True)."""
+        signal = self.preprocess(signal, kwargs.get("norm", True))
+        output = self.batch_predict(signal, (len(signal), 1, *self.output_dim), kwargs.get("num_batches", 10))
+        return output[:, 0].numpy()
+
+    def run(self, signal: np.ndarray, **kwargs: int) -> np.ndarray:
+        start_time = time.time()
+        prediction = self.predict(signal, **kwargs)
+        if self.verbose:
+            one = prediction.shape[0] == 1
+            what = (" image was " if one else " images were ") if len(self.output_dim) == 1 else \
+                (" spectrum was " if one else " spectra were ")
+            print("\n" + str(prediction.shape[0]) + what + "decoded in approximately "
+                  + str(np.around(time.time() - start_time, decimals=4)) + ' seconds')
+        return prediction

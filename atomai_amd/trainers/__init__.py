@@ -1,6 +1,6 @@
 from .etrainer import BaseEnsembleTrainer, EnsembleTrainer
 from .gptrainer import dklGPTrainer
-from .trainer import BaseTrainer, SegTrainer
+from .trainer import BaseTrainer, ImSpecTrainer, SegTrainer
 from .vitrainer import viBaseTrainer
 
-__all__ = ["BaseTrainer", "SegTrainer", "viBaseTrainer", "dklGPTrainer", "BaseEnsembleTrainer", "EnsembleTrainer"]
+__all__ = ["BaseTrainer", "SegTrainer", "ImSpecTrainer", "viBaseTrainer", "dklGPTrainer", "BaseEnsembleTrainer", "EnsembleTrainer"]

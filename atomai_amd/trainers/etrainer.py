@@ -2,7 +2,8 @@
 
 Same orchestration (train_baseline / train_ensemble_from_scratch / train_ensemble_from_baseline / train_swag),
 attribute names and ``*_ensemble_metadict.tar`` format; every member trains on the HIP engine through
-``BaseTrainer``.  Only the segmentation families are in scope ('imspec' raises).
+``BaseTrainer``.  Only the segmentation families are in scope: ensembles of ImSpec models raise (single ones train with
+``models.ImSpec`` / ``trainers.ImSpecTrainer``).
 
 Multi-GPU (no counterpart in the reference): members are independent training runs, so under an
 initialised process group ``distributed=True`` gives rank r the members r, r + world, ... on its own GPU — no
@@ -170,7 +171,8 @@ class EnsembleTrainer(BaseEnsembleTrainer):
                 self.net, self.meta_state_dict = init_fcnn_model(model, self.nb_classes, **kwargs)
                 self.accuracy_fn = accuracy_fn_seg(nb_classes)
             elif model == "imspec":
-                raise NotImplementedError("the ImSpec family is outside the MI355X hot path of this build")
+                raise NotImplementedError("ensembles of ImSpec models are outside the MI355X hot path of this build "
+                                          "(single models: aoi.models.ImSpec)")
             else:
                 raise NotImplementedError("Currently implemented models are 'Unet', 'dilnet', SegResNet', "
                                           "and 'ResHedNet'")

@@ -1,4 +1,4 @@
-"""BaseTrainer / SegTrainer on the MI355X hot path (reference: atomai/trainers/trainer.py:42-737).
+"""BaseTrainer / SegTrainer / ImSpecTrainer on the MI355X hot path (reference: atomai/trainers/trainer.py:42-857).
 
 Same attributes (net, optimizer, criterion, loss_acc, meta_state_dict, X_train ...), same batch schedule
 (sklearn shuffle with batch_seed), same train/test-step order and checkpoint format.  Differences, all
@@ -16,10 +16,10 @@ import numpy as np
 import torch
 
 from .. import losses_metrics
-from ..nets import init_fcnn_model
+from ..nets import init_fcnn_model, init_imspec_model
 from ..optim import FusedAdam
 from ..utils import (array2list, average_weights, gpu_usage_map, init_dataloaders, init_fcnn_dataloaders,
-                     preprocess_training_image_data,
+                     init_imspec_dataloaders, preprocess_training_image_data, preprocess_training_imspec_data,
                      reset_bnorm, set_train_rng, weights_init)
 
 warnings.filterwarnings("ignore", module="torch.nn.functional")
@@ -435,3 +435,45 @@ class SegTrainer(BaseTrainer):
         """Mean IoU of the mini-batch (trainer.py:727-737).  As in the reference the third positional argument of
         ``IoU`` — ``activation`` — receives ``self.nb_classes`` (truthy): the logits go through softmax / sigmoid."""
         return losses_metrics.IoU(y, y_prob, self.nb_classes).evaluate()
+
+
+class ImSpecTrainer(BaseTrainer):
+    """Trainer of the image -> spectrum and spectrum -> image networks (trainer.py:740-857): ``SignalED`` from
+    ``init_imspec_model`` with the reference's keyword arguments (seed, batch_seed, nblayers_encoder / _decoder,
+    nbfilters_encoder / _decoder, batch_norm, encoder_downsampling, decoder_upsampling).  The step loop, the batch
+    schedule and the checkpoint are BaseTrainer's; the criterion is the one-pass MSE (losses_metrics.MSELoss) and Adam is
+    the fused flat optimizer, as for SegTrainer."""
+
+    def __init__(self, in_dim: Tuple[int], out_dim: Tuple[int], latent_dim: int = 2,
+                 **kwargs: Union[int, bool, str]) -> None:
+        super().__init__()
+        seed = kwargs.get("seed", 1)
+        kwargs["batch_seed"] = kwargs.get("batch_seed", seed)
+        self._batch_seed = kwargs["batch_seed"]
+        set_train_rng(seed)
+        self.in_dim, self.out_dim = in_dim, out_dim
+        self.net, self.meta_state_dict = init_imspec_model(in_dim, out_dim, latent_dim, **kwargs)
+        self.net.to(self.device)
+        if self.device == 'cpu':
+            warnings.warn("No GPU found: the MI355X kernels cannot run (there is no CPU fallback)", UserWarning)
+        self.meta_state_dict["weights"] = self.net.state_dict()
+
+    def set_data(self, X_train, y_train, X_test=None, y_test=None, **kwargs) -> None:
+        """Features and targets as (n, 1, h, w) images / (n, 1, l) spectra, or without the channel axis (added with a
+        warning); without a test set 15 % of the data is split off (trainer.py:801-857)."""
+        if X_test is None or y_test is None:
+            from sklearn.model_selection import train_test_split
+            X_train, X_test, y_train, y_test = train_test_split(
+                X_train, y_train, test_size=kwargs.get("test_size", .15), shuffle=True,
+                random_state=kwargs.get("seed", 1))
+        alloc = kwargs.get("memory_alloc", 4)
+        if self.full_epoch:
+            self.train_loader, self.test_loader, dims = init_imspec_dataloaders(
+                X_train, y_train, X_test, y_test, self.batch_size, alloc)
+        else:
+            (self.X_train, self.y_train, self.X_test, self.y_test,
+             dims) = preprocess_training_imspec_data(X_train, y_train, X_test, y_test, self.batch_size, alloc)
+        self.data_is_set = True
+        if tuple(dims[0]) != tuple(self.in_dim) or tuple(dims[1]) != tuple(self.out_dim):
+            raise AssertionError("The input/output dimensions of the model must match the height, width and length "
+                                 "(for spectra) of training")

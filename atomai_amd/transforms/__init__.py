@@ -1,3 +1,3 @@
-from .imaug import datatransform, seg_augmentor  # noqa: F401
+from .imaug import datatransform, imspec_augmentor, seg_augmentor  # noqa: F401
 
-__all__ = ["datatransform", "seg_augmentor"]
+__all__ = ["datatransform", "seg_augmentor", "imspec_augmentor"]

@@ -353,6 +353,18 @@ class datatransform:
         return x[:, None], targets
 
 
+def imspec_augmentor(in_dim, out_dim, **kwargs) -> Optional[Callable]:
+    """None when no augmentation keyword is given, as the reference (imaug.py:435-458).  Its augmentor for image ->
+    spectrum models runs on the host in numpy between the steps; that is not on the HIP path here: the keywords raise."""
+    auglist = ["custom_transform", "gauss_noise", "jitter", "poisson_noise", "contrast", "salt_and_pepper", "blur",
+               "background"]
+    given = [k for k in auglist if k in kwargs]
+    if not given:
+        return None
+    raise NotImplementedError(f"on-the-fly augmentation of im2spec / spec2im data ({', '.join(given)}) is outside the "
+                              "MI355X hot path of this build")
+
+
 def seg_augmentor(nb_classes: int, **kwargs) -> Optional[Callable]:
     """``augmentor(images, labels, seed)`` for BaseTrainer.data_augmentation / Segmentor.fit(..., rotation=True, ...)
     (imaug.py:398-432); None when no augmentation keyword is given."""

@@ -1,5 +1,5 @@
-"""numpy -> tensor plumbing for Segmentor training / prediction
-(reference: atomai/utils/preproc.py:18-74, 138-278, 365-421, 798-825)."""
+"""numpy -> tensor plumbing for Segmentor and ImSpec training / prediction
+(reference: atomai/utils/preproc.py:18-135, 138-362, 365-441, 798-854)."""
 import warnings
 
 import numpy as np
@@ -29,6 +29,28 @@ def check_image_dims(X_train, y_train, X_test, y_test, num_classes: int):
     if num_classes == 1:
         y_train, y_test = chan(y_train, "training labels"), chan(y_test, "test labels")
     return X_train, y_train, X_test, y_test
+
+
+def check_signal_dims(X_train, y_train, X_test, y_test):
+    """ImSpec data: adds the channel axis of 1 to image stacks passed as (n, h, w) and spectra passed as (n, l).  Which
+    side holds the images is read off the ranks: the features have more axes than the targets (im2spec) or fewer
+    (spec2im); with equal ranks nothing is touched (atomai/utils/preproc.py:77-135)."""
+    def chan(a, bare_ndim, what):
+        if a.ndim == bare_ndim:
+            warnings.warn(f'Adding a channel dimension of 1 to {what}', UserWarning)
+            return a[:, None]
+        return a
+    if X_train.ndim == y_train.ndim:
+        return X_train, y_train, X_test, y_test
+    # as in the reference both messages name the features "images" and the targets "spectra"
+    x_bare, y_bare = (3, 2) if X_train.ndim > y_train.ndim else (2, 3)
+    X_train, X_test = chan(X_train, x_bare, "training images"), chan(X_test, x_bare, "test images")
+    y_train, y_test = chan(y_train, y_bare, "training spectra"), chan(y_test, y_bare, "test spectra")
+    out = (X_train, y_train, X_test, y_test)
+    # (the reference compares the train / test shapes in its spec2im branch only; kept, so that the same calls raise)
+    if X_train.ndim < y_train.ndim and (out[0].shape[1:] != out[2].shape[1:] or out[1].shape[1:] != out[3].shape[1:]):
+        raise ValueError("The image/spectra dimensions must be the same for training and test data")
+    return out
 
 
 def get_array_memsize(X_arr, precision: str = "single") -> float:
@@ -97,6 +119,47 @@ def init_fcnn_dataloaders(X_train, y_train, X_test, y_test, batch_size: int, num
                           memory_alloc: float = 4):
     *tensors, num_classes = preprocess_training_image_data_(X_train, y_train, X_test, y_test)
     return (*init_dataloaders(*tensors, batch_size, memory_alloc), num_classes)
+
+
+def preprocess_training_imspec_data_(X_train, y_train, X_test, y_test):
+    """float32 tensors with a channel axis + ((input dims), (output dims)) (atomai/utils/preproc.py:281-313)."""
+    data = (X_train, y_train, X_test, y_test)
+    all_np = all(isinstance(i, np.ndarray) for i in data)
+    all_t = all(isinstance(i, torch.Tensor) for i in data)
+    if not all_np and not all_t:
+        raise TypeError("Provide training and test data in the form of numpy arrays or torch tensors")
+    X, y, Xt, yt = check_signal_dims(*data)
+    dims = (tuple(X.shape[2:]), tuple(y.shape[2:]))
+    if all_np:
+        X, y, Xt, yt = (torch.from_numpy(np.ascontiguousarray(a)) for a in (X, y, Xt, yt))
+    return X.float(), y.float(), Xt.float(), yt.float(), dims
+
+
+def preprocess_training_imspec_data(X_train, y_train, X_test, y_test, batch_size: int, memory_alloc: float = 4):
+    """Lists of whole mini-batches for the im2spec / spec2im trainers + the data's (in_dim, out_dim)
+    (atomai/utils/preproc.py:316-362)."""
+    *tensors, dims = preprocess_training_imspec_data_(X_train, y_train, X_test, y_test)
+    return (*array2list(*tensors, batch_size, memory_alloc), dims)
+
+
+def init_imspec_dataloaders(X_train, y_train, X_test, y_test, batch_size: int, memory_alloc: float = 4):
+    """(train loader, test loader, (in_dim, out_dim)) (atomai/utils/preproc.py:424-441)."""
+    *tensors, dims = preprocess_training_imspec_data_(X_train, y_train, X_test, y_test)
+    return (*init_dataloaders(*tensors, batch_size, memory_alloc), dims)
+
+
+def torch_format_spectra(spectra: np.ndarray, norm: bool = False) -> torch.Tensor:
+    """(n, l) -> float32 (n, 1, l); optional global min-max normalisation over the WHOLE stack
+    (atomai/utils/preproc.py:828-854)."""
+    if spectra.ndim not in (2, 3):
+        raise AssertionError("Provide spectrum(s) as 2D (n, length) or 3D (n, 1, length) tensor")
+    if spectra.ndim == 2:
+        spectra = spectra[:, None]
+    elif spectra.shape[1] != 1:
+        raise AssertionError("3D spectra tensor must have (n, 1, length) dimensions")
+    if norm:
+        spectra = (spectra - spectra.min()) / np.ptp(spectra)
+    return torch.from_numpy(np.ascontiguousarray(spectra)).float()
 
 
 def torch_format_image(image_data: np.ndarray, norm: bool = True) -> torch.Tensor:

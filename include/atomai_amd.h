@@ -571,6 +571,48 @@ int amx_locate_emit(const void* work, int B, int H, int W, int nch, int dist_edg
 int amx_adam_flat(float* p, const float* g, float* m, float* v, long n, float lr, double b1, double b2,
                   float eps, double bc1, double bc2, float gscale, void* stream);
 
+/* ---- ImSpec (im2spec / spec2im): nn.Conv1d(k=3|1, stride 1, padding=dilation) + bias + LeakyReLU + BatchNorm1d batch
+ * statistics, csrc/conv1d.hip.  atomai/nets/blocks.py:61-76 (ConvBlock, ndim=1), :300-318 (DilatedBlock, ndim=1);
+ * atomai/nets/ed.py:20-157 (SignalEncoder / SignalDecoder).  Activations are the tape's NHWC tensors with H = 1:
+ * x [N][L][Cs], y [N][L][round_up(cout,4)] fp32; (sc, sh): the producer's BatchNorm affine (both or neither), then
+ * LeakyReLU(in_slope) (1 = none), applied on load; padding positions contribute zero AFTER the affine and nothing crosses
+ * a sample boundary.  Weights stay (O, I, taps) fp32 at the ABI and are re-imaged by amx_pack_weights1d (size
+ * amx_pack_weights1d_size floats): mode 0 = forward; mode 1 = data gradient — amx_conv1d_fwd(x = dpre, Cs =
+ * round_up(cout,4), "cout" = Cin, no bias, slopes 1) then writes d loss / d input [N][L][Cin_s].
+ * stats != NULL: [rows][2][round_up(cout,16)] rows (sum, M2) over rows_pix consecutive positions = amx_bn_finalize /
+ * amx_bn_stats_merge mode 1 (rows = amx_rows_for(N*L), rows_pix = amx_rows_pix(N*L)); stats == NULL: rows, rows_pix ignored.
+ * Limits (amx_conv1d_supported; refused with the argument named in amx_last_error): Cs % 4 == 0, cout <= 1024, taps 3 or
+ * 1, any dil >= 1 whose window of 64 + 2*dil positions x (round_up(Cs,16) + 4) floats plus 4 KB of reduction buffer fits
+ * 160 KB of LDS (dil >= L: only the centre tap sees data, no window).  fp32 MFMA (v_mfma_f32_16x16x4_f32), fixed summation order. */
+long amx_pack_weights1d_size(int cout, int Cin_s, int taps);
+int amx_pack_weights1d(const float* w_oit, float* dst, int cout, int cin, int Cin_s, int taps, int mode, void* stream);
+int amx_conv1d_supported(int Cs, int cout, int L, int taps, int dil);
+int amx_conv1d_fwd(const float* x, const float* sc, const float* sh, float in_slope, int Cs, const float* wpk,
+                   const float* bias, float* y, float* stats, int N, int L, int cout, int taps, int dil, float slope,
+                   int rows, int rows_pix, void* stream);
+/* dW[o][i][t] = sum_{n,l} dpre[n][l][o] * xin[n][l + (t - taps/2) dil][i] (xin: x after the affine / input activation,
+ * zero outside [0, L)) as partial rows part [rows][taps][round_up(Cs,16)][round_up(cout,16)], rows =
+ * amx_conv1d_wgrad_rows(N, L) position ranges: fold with amx_reduce_rows_chunked / amx_wgrad_reduce.  bpart != NULL:
+ * [rows][round_up(cout,16)] column sums of dpre (the bias gradient; amx_reduce_rows).  dpre: [N][L][round_up(cout,4)], the
+ * tensor amx_bn_bwd_apply writes.  No floating-point atomics: two runs give the same bits. */
+int amx_conv1d_wgrad_rows(int N, int L);
+int amx_conv1d_wgrad_supported(int Cs, int cout, int L, int taps, int dil);
+int amx_conv1d_wgrad(const float* x, const float* sc, const float* sh, float in_slope, int Cs, const float* dpre,
+                     float* part, float* bpart, int N, int L, int cout, int taps, int dil, int rows, void* stream);
+/* csrc/signal.hip.  F.interpolate(scale_factor=2, mode="nearest") on (N, C, L) (ed.py:152-154), channels-last
+ * v [N][L][Cs] -> u [N][2L][Cs], and its backward dv = du[2l] + du[2l+1].  Nearest interpolation commutes with a
+ * per-channel affine: the tape upsamples the raw tensor and carries the producer's (scale, shift) on. */
+int amx_upsample1d2x_fwd(const float* v, float* u, int N, int L, int Cs, void* stream);
+int amx_upsample1d2x_bwd(const float* du, float* dv, int N, int L, int Cs, void* stream);
+/* F.avg_pool1d(x, k, k) (H = 1, kh = 1) / F.avg_pool2d(x, k, k) of the one-channel net input (ed.py:70-76), floor
+ * semantics: x [N][H][W] -> y [N][H/kh][W/kw].  Forward only. */
+int amx_avgpool_fwd(const float* x, float* y, int N, int H, int W, int kh, int kw, void* stream);
+/* torch.nn.MSELoss(reduction="mean") and its gradient in one pass (trainer.py:740-857: ImSpecTrainer's criterion):
+ * part [amx_mse_rows(n)] block sums of (p - t)^2 (the loss = amx_reduce_rows(part, rows, 1, 1, 1/n)), grad = 2 (p - t) / n
+ * (or NULL).  Deterministic two-stage sum. */
+int amx_mse_rows(long n);
+int amx_mse_fwd_bwd(const float* p, const float* t, float* grad, float* part, long n, int rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

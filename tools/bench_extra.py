@@ -1,5 +1,5 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) — one JSON line each, written to gpurun_out/.
-   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses
+   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec
 """
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -564,11 +564,133 @@ def bench_losses(hw=512, bs=32, steps=10, warmup=4, reps=3, emit=True):
     return out
 
 
+class _TorchSignalED(torch.nn.Module):
+    """The SignalED stack (atomai/nets/ed.py:20-228, no down / upsampling) from stock torch.nn modules: the outside
+    yardstick of bench_imspec on the same GPU."""
+
+    def __init__(self, in_dim, out_dim, latent_dim, nl_e=3, nl_d=4, nf_e=64, nf_d=64):
+        super().__init__()
+        nn = torch.nn
+
+        def pick(dim):
+            return (nn.Conv2d, nn.BatchNorm2d) if len(dim) == 2 else (nn.Conv1d, nn.BatchNorm1d)
+
+        def layer(dim, cin, cout, dil=1):
+            conv, bn = pick(dim)
+            return nn.Sequential(conv(cin, cout, 3, padding=dil, dilation=dil), nn.LeakyReLU(0.1), bn(cout))
+        self.enc = nn.Sequential(*[layer(in_dim, 1 if i == 0 else nf_e, nf_e) for i in range(nl_e)])
+        self.fc_e = nn.Linear(nf_e * int(np.prod(in_dim)), latent_dim)
+        self.fc_d = nn.Linear(latent_dim, nf_d * int(np.prod(out_dim)))
+        self.shape = (nf_d, *out_dim)
+        self.dil = nn.ModuleList([layer(out_dim, nf_d, nf_d, d + 1) for d in range(nl_d)])
+        self.conv = layer(out_dim, nf_d, 1)
+        self.out = pick(out_dim)[0](1, 1, 1)
+
+    def forward(self, x):
+        z = self.fc_e(self.enc(x).flatten(1))
+        h = self.fc_d(z).reshape(-1, *self.shape)
+        tot = 0
+        for blk in self.dil:                       # DilatedBlock: the sum of every sub-layer output
+            for m in blk:
+                h = m(h)
+                tot = tot + h
+        return self.out(self.conv(tot))
+
+
+def bench_imspec(reps=3, iters=20, steps=10, warmup=4, emit=True):
+    """ImSpec (im2spec).  (a) interleaved in-process A/B of amx_conv1d_fwd against the only in-tree baseline, the H = 1
+    embedding through amx_conv2d_fwd (three taps in the middle row of a zero 3x3 weight), at (N, L, Cin -> Cout, dil) =
+    (64, 64, 64 -> 64, 1) and (256, 1024, 64 -> 64, 4): min of `reps` rounds of `iters` launches, us per launch.
+    (b) a whole training step of the default im2spec (16, 16) -> (64,), bs 64, and (16, 16) -> (1024,), bs 256, next to
+    the same stack from stock torch.nn modules (_TorchSignalED, torch.optim.Adam, nn.MSELoss) on the same GPU: median of
+    `reps` rounds of `steps` steps, ms per step."""
+    dev = "cuda"
+    res = {"conv1d_fwd_vs_h1_embedding_us": {}, "train_step_ms": {}}
+    lib = L.load()
+    for N, Ln, C, dil in ((64, 64, 64, 1), (256, 1024, 64, 4)):
+        x = torch.randn(N, Ln, C, device=dev)
+        w = torch.randn(C, C, 3, device=dev) / (3 * C) ** 0.5
+        b = torch.randn(C, device=dev)
+        w2 = torch.zeros(C, C, 3, 3, device=dev)
+        w2[:, :, 1, :] = w
+        sp = L.stream_ptr(x)
+        p1 = torch.empty(lib.amx_pack_weights1d_size(C, C, 3), device=dev)
+        L.call("amx_pack_weights1d", L.ptr(w), L.ptr(p1), C, C, C, 3, 0, sp)
+        p2 = torch.empty(lib.amx_pack_weights_size(C, C, 0, 9, 0), device=dev)
+        L.call("amx_pack_weights", L.ptr(w2), L.ptr(p2), C, C, C, 0, 0, 9, 0, sp)
+        y1, y2 = torch.empty(N, Ln, C, device=dev), torch.empty(N, 1, Ln, C, device=dev)
+
+        def run1():
+            L.call("amx_conv1d_fwd", L.ptr(x), None, None, 1.0, C, L.ptr(p1), L.ptr(b), L.ptr(y1), None, N, Ln, C, 3, dil,
+                   0.1, 0, 0, sp)
+
+        def run2():
+            L.call("amx_conv2d_fwd", L.ptr(x), None, None, C, None, None, None, 0, L.ptr(p2), L.ptr(b), None, L.ptr(y2), C,
+                   None, 0, None, N, 1, Ln, C, 9, dil, 0.1, sp)
+        for f in (run1, run2):
+            for _ in range(3):
+                f()
+        t = {"conv1d": [], "h1_embedding": []}
+        for _ in range(reps):
+            for name, f in (("conv1d", run1), ("h1_embedding", run2)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    f()
+                e1.record()
+                torch.cuda.synchronize()
+                t[name].append(e0.elapsed_time(e1) / iters * 1e3)
+        diff = float((y1 - y2.view(N, Ln, C)).abs().max())
+        res["conv1d_fwd_vs_h1_embedding_us"][f"{N}x{Ln}x{C}_dil{dil}"] = {
+            "conv1d": round(min(t["conv1d"]), 2), "h1_embedding": round(min(t["h1_embedding"]), 2),
+            "rounds": {k: [round(v, 2) for v in vs] for k, vs in t.items()}, "max_abs_diff": diff}
+    rs = np.random.RandomState(0)
+    for out_len, bs in ((64, 64), (1024, 256)):
+        X = rs.rand(bs, 1, 16, 16).astype(np.float32)
+        Y = rs.rand(bs, 1, out_len).astype(np.float32)
+        m = aoi.models.ImSpec((16, 16), (out_len,), latent_dim=10, seed=1)
+        m.compile_trainer((X, Y, X, Y), loss="mse", training_cycles=1, batch_size=bs, plot_training_history=False)
+        torch.manual_seed(1)
+        ref = _TorchSignalED((16, 16), (out_len,), 10).to(dev)
+        opt, crit = torch.optim.Adam(ref.parameters(), lr=1e-3), torch.nn.MSELoss()
+        xt, yt = torch.from_numpy(X).to(dev), torch.from_numpy(Y).to(dev)
+
+        def ours():
+            return m.train_step(m.X_train[0], m.y_train[0])[0]
+
+        def stock():
+            ref.train()
+            opt.zero_grad()
+            loss = crit(ref(xt), yt)
+            loss.backward()
+            opt.step()
+            return loss.item()
+        for f in (ours, stock):
+            for _ in range(warmup):
+                f()
+        t = {"atomai_amd": [], "torch_nn": []}
+        for _ in range(reps):
+            for name, f in (("atomai_amd", ours), ("torch_nn", stock)):
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                for _ in range(steps):
+                    f()
+                torch.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) / steps * 1e3)
+        res["train_step_ms"][f"16x16_to_{out_len}_bs{bs}"] = {
+            k: {"median": round(float(np.median(v)), 3), "rounds": [round(u, 3) for u in v]} for k, v in t.items()}
+    first = res["train_step_ms"]["16x16_to_64_bs64"]
+    out = {"metric": "ImSpec im2spec (16, 16) -> (64,) training step, bs=64", "unit": "ms",
+           "value": first["atomai_amd"]["median"], "higher_is_better": False, "detail": res}
+    if emit:
+        print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["rvae", "predict"]
     os.makedirs("gpurun_out", exist_ok=True)
     res = {}
     for w in what:
-        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "segfamily": bench_segfamily, "losses": bench_losses,
+        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)
