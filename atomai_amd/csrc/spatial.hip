@@ -57,7 +57,8 @@ extern "C" int amx_pool2x2_fwd(const float* a, const float* scale, const float* 
 // Backward: dy[full res] = skip_grad (optional) + route(g) where the gradient of each 2x2 window goes
 // to its FIRST maximum in scan order (torch semantics); the arg-max is recomputed from a + affine.
 // bstats (optional): [gridDim.x][2][4G] per-block (sum dy, sum dy*a) of the producer layer's BatchNorm backward;
-// requires (gridDim.x * 256) % G == 0 so that a thread keeps its channel group.
+// requires (gridDim.x * 256) % G == 0 so that a thread keeps its channel group, and 2 * G <= 256: thread (which, cg) of the
+// final reduction writes one float4 of the block's row.
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__ g, const float* __restrict__ a,
                                 const float* __restrict__ scale, const float* __restrict__ shift,
                                 const float* __restrict__ skip, float* __restrict__ dy, int N, int H,
@@ -148,7 +149,7 @@ extern "C" int amx_pool2x2_bwd(const float* g, const float* a, const float* scal
                                void* stream) {
     if (!g || !a || !dy || (Cs & 3) || Cs <= 0 || H < 2 || W < 2) AMX_BADARG(1);
     if ((scale == nullptr) != (shift == nullptr)) AMX_BADARG(2);
-    if (bstats && (256 % (Cs / 4)) != 0) AMX_BADARG(3);
+    if (bstats && ((256 % (Cs / 4)) != 0 || Cs / 4 > 128)) AMX_BADARG(3);
     const size_t total = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (Cs / 4);
     AMX_LAUNCH(pool_bwd_kernel, dim3(pool_bwd_blocks(total)), dim3(256), 0, (hipStream_t)stream, g, a, scale,
                shift, skip, dy, N, H, W, Cs / 4, bstats);

@@ -983,7 +983,7 @@ class PoolNode(_Node):
             s.grad = _empty(s.t.shape, s.t)
             skip = s.gx
         bstats = None
-        if s.wants_bstats(self, tape.training) and 256 % (s.Cs // 4) == 0:
+        if s.wants_bstats(self, tape.training) and 256 % (s.Cs // 4) == 0 and s.Cs // 4 <= 128:   # (else: amx_bn_bwd_reduce)
             rows = L.load().amx_pool2x2_bwd_rows(s.N, s.H, s.W, s.Cs)
             bstats = _empty((rows, 2, s.Cs), g)
             s.bstats = (bstats, rows, s.Cs, 0)

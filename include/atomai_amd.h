@@ -241,6 +241,8 @@ int amx_pool2x2_fwd(const float* a, const float* scale, const float* shift, floa
                     int Cs, void* stream);
 int amx_pool2x2_bwd(const float* g, const float* a, const float* scale, const float* shift,
                     const float* skip, float* dy, float* bstats, int N, int H, int W, int Cs, void* stream);
+/* bstats [amx_pool2x2_bwd_rows][2][Cs] or NULL: per-block (sum dy, sum dy * a) of the producer's BatchNorm backward; only for
+ * G = Cs / 4 with 256 % G == 0 and G <= 128 (otherwise refused: amx_bn_bwd_reduce computes the sums). */
 /* amx_pool2x2_bwd for the output of the net's FIRST layer (conv(1 -> F) 3x3 -> LeakyReLU -> BatchNorm -> max-pool,
  * atomai/nets/fcnn.py:83-84,121-122; the input needs no gradient) fused with that layer's weight gradient: dy is formed in
  * registers and never written; besides bstats it emits part3 [rows][3][10][Cs], the three sums the first-layer weight /
