@@ -333,6 +333,9 @@ extern "C" int amx_px_bwd(const float* dl, const float* a, const float* scale, c
 // LOSS == 2 (focal_loss, losses.py:13-50; KT == 1): the BCE form with the gradient times the device scalar dtab[0] = dF/dc
 // (amx_focal_from_bce of the mean BCE a first pass, amx_px_bce_sum, has formed).  The CE / BCE instantiations (LOSS == 0) do
 // not read the two extra arguments.
+// LOSS == 3 (MSELoss, mean; KT == 1): the regression head of the denoising autoencoder (atomai/models/denoiser.py: the
+// decoder ends in Conv2d(C, 1, 1) and trains with MSE).  p = the one "logit", lterm = (p - t)^2 against the float target,
+// g = 2 (p - t) / npix; everything downstream of g is the code of the other kinds.
 template <int KT, bool BCE = false, int LOSS = 0>
 __global__ __launch_bounds__(256) void px_ce_train_kernel(const float* __restrict__ a, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, const float* __restrict__ w,
@@ -404,7 +407,11 @@ __global__ __launch_bounds__(256) void px_ce_train_kernel(const float* __restric
                 lg[k] = t + bk[k];
             }
             float gk[KT], lterm;
-            if (DICE && BCE) {                    // dlogit = s (1 - s) (g_fg - g_bg)
+            if (LOSS == 3) {
+                const float df = lg[0] - tf[u];
+                lterm = df * df;
+                gk[0] = 2.f * df * ic;
+            } else if (DICE && BCE) {                    // dlogit = s (1 - s) (g_fg - g_bg)
                 const float xv = lg[0], e = expf(-fabsf(xv));
                 const float sg = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
                 const float2 fg = ab[DICE ? u : 0][0], bg = ab[DICE ? u : 0][DICE ? 1 : 0];
@@ -574,6 +581,25 @@ extern "C" int amx_px_focal_train(const float* a, const float* scale, const floa
     AMX_LAUNCH((px_ce_train_kernel<1, true, 2>), dim3(rows), dim3(256), lds, (hipStream_t)stream, a, scale, shift, w, b,
                (const long long*)nullptr, target_f, dxn, part, partb, bstats, lpart, npix, C, Cs, rows_pix,
                1.0f / (float)npix, dfdc, 1);
+    AMX_CHECK_LAUNCH();
+    return 0;
+}
+
+// px forward + MSE (mean) + px backward, one output channel: the tail of a DenoisingAutoencoder training step.  target_f
+// [N][1][H][W]; lpart [rows] as for amx_px_ce_train.
+extern "C" int amx_px_mse_train(const float* a, const float* scale, const float* shift, const float* w, const float* b,
+                                const float* target_f, float* dxn, float* part, float* partb, float* bstats,
+                                float* lpart, int N, int H, int W, int C, int Cs, int rows, int rows_pix, void* stream) {
+    if (!a || !w || !b || !target_f || !dxn || !part || !partb || !lpart || C <= 0 || Cs < C) AMX_BADARG(1);
+    if (!amx_px_ce_train_supported(Cs, 1)) AMX_BADARG(2);
+    if ((scale == nullptr) != (shift == nullptr)) AMX_BADARG(3);
+    const long npix = (long)N * H * W;
+    if (rows <= 0 || rows_pix <= 0 || (long)rows * rows_pix < npix) AMX_BADARG(4);
+    const int PL = 256 / (Cs / 4);
+    const size_t lds = ((size_t)PL * Cs + (size_t)PL + 4 + (size_t)2 * PL * Cs + 256) * sizeof(float);
+    AMX_LAUNCH((px_ce_train_kernel<1, true, 3>), dim3(rows), dim3(256), lds, (hipStream_t)stream, a, scale, shift, w, b,
+               (const long long*)nullptr, target_f, dxn, part, partb, bstats, lpart, npix, C, Cs, rows_pix,
+               1.0f / (float)npix, (const float*)nullptr, 1);
     AMX_CHECK_LAUNCH();
     return 0;
 }

@@ -51,6 +51,9 @@ FUSE_HEAD = os.environ.get("AMX_FUSE_HEAD", "1") != "0"
 FUSE_POOL = os.environ.get("AMX_FUSE_POOL", "1") != "0"
 # the training step's head, loss and their backward in one pass (PxLossNode); AMX_FUSE_PX_LOSS=0 keeps the logits
 FUSE_PX_LOSS = os.environ.get("AMX_FUSE_PX_LOSS", "1") != "0"
+# the 'mse' kind of that node (the denoiser's head, amx_px_mse_train): a switch of its own below FUSE_PX_LOSS, OFF by default:
+# 2.874 vs 2.903 ms per step against px_fwd -> mse_fwd_bwd -> px_bwd, inside the A/A spread of 0.170 ms (profiles/denoiser_head_ab.log)
+FUSE_PX_MSE = os.environ.get("AMX_FUSE_PX_MSE", "0") != "0"
 
 
 def bwd_fuse_enabled() -> bool:
@@ -1284,7 +1287,8 @@ class PxLossNode(_Node):
     kind 'dice' (criterion: losses.dice_loss): amx_px_dice_sums -> the coefficient table and the loss (amx_dice_finalize) ->
     amx_px_dice_train, two passes over the last activation, the logits still never written.  kind 'focal' (losses.focal_loss,
     one class), two passes as well: amx_px_bce_sum -> the mean BCE c -> value = F(c) and dF/dc (amx_focal_from_bce, device
-    scalars) -> amx_px_focal_train, the BCE form with dF/dc folded into the logits gradient (a pass over dxn would cost more)."""
+    scalars) -> amx_px_focal_train, the BCE form with dF/dc folded into the logits gradient (a pass over dxn would cost more).
+    kind 'mse' (losses.MSELoss, mean; one output channel: the denoiser's head): amx_px_mse_train -> amx_reduce_rows."""
 
     def __init__(self, tape, src: Act, conv, target: torch.Tensor, kind: str = "ce", criterion=None):
         self.src, self.conv = src, conv
@@ -1292,7 +1296,7 @@ class PxLossNode(_Node):
         K = conv.weight.shape[0]
         assert conv.weight.shape[1] == src.C and conv.weight.shape[2:] == (1, 1)
         assert target.numel() == src.npix and target.dtype == (torch.float32 if K == 1 else torch.int64)
-        assert kind in ("ce", "dice", "focal") and (kind != "focal" or K == 1)
+        assert kind in ("ce", "dice", "focal", "mse") and (kind not in ("focal", "mse") or K == 1)
         self.K, self.kind = K, kind
         s = src
         rows = L.load().amx_rows_for(s.npix)
@@ -1326,6 +1330,12 @@ class PxLossNode(_Node):
             lpart = _empty((rows,), s.t)
             L.call("amx_px_focal_train", *head[:5], head[6], L.ptr(dfdc), L.ptr(self.dxn), L.ptr(self.part),
                    L.ptr(self.partb), L.ptr(self.bstats), L.ptr(lpart), s.N, s.H, s.W, s.C, s.Cs, rows, rows_pix, sp)
+        elif kind == "mse":
+            lpart = _empty((rows,), s.t)
+            L.call("amx_px_mse_train", *head[:5], head[6], L.ptr(self.dxn), L.ptr(self.part), L.ptr(self.partb),
+                   L.ptr(self.bstats), L.ptr(lpart), s.N, s.H, s.W, s.C, s.Cs, rows, rows_pix, sp)
+            self.value = torch.empty((), dtype=torch.float32, device=s.t.device)
+            L.call("amx_reduce_rows", L.ptr(lpart), rows, 1, 1, 1.0 / s.npix, L.ptr(self.value), sp)
         else:
             lpart = _empty((rows,), s.t)
             L.call("amx_px_ce_train", *head, L.ptr(self.dxn), L.ptr(self.part), L.ptr(self.partb),
@@ -1372,8 +1382,11 @@ def px_loss_fusable(src: Act, conv, target, kind: str = "ce") -> bool:
         return False
     if kind == "dice":
         return bool(L.load().amx_px_dice_train_supported(src.Cs, K, src.W))
-    if kind == "focal" and K != 1:
+    if kind in ("focal", "mse") and K != 1:
         return False
+    if kind == "mse":
+        return FUSE_PX_MSE and tuple(target.shape) == (src.N, 1, src.H, src.W) and bool(
+            L.load().amx_px_ce_train_supported(src.Cs, 1))
     return kind in ("ce", "focal") and bool(L.load().amx_px_ce_train_supported(src.Cs, K))
 
 

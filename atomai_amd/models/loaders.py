@@ -6,7 +6,9 @@ atomai/trainers/trainer.py:344-358 and atomai/trainers/vitrainer.py:361-377 in t
 written by the reference loads here onto the HIP modules (same state-dict keys / shapes), and files written
 here hold only torch types (the fused optimizer is stored as its ``torch.optim.Adam`` equivalent).
 
-Model families outside SURVEY.md section 8 (reg / cls / denoising autoencoder) raise, and so do ImSpec ensembles.
+"denoising_autoencoder" checkpoints rebuild a DenoisingAutoencoder (load_denoising_autoencoder; a file without the
+"use_batch_norm" entry is rebuilt WITH BatchNorm, as the reference's loader does).  Model families outside SURVEY.md
+section 8 (reg / cls: torchvision backbones) raise, and so do ImSpec and denoiser ensembles.
 """
 import warnings
 from copy import deepcopy as dc
@@ -15,11 +17,12 @@ from typing import Dict, Tuple, Type, Union
 import torch
 
 from ..utils import average_weights
+from .denoiser import DenoisingAutoencoder
 from .dgm import VAE, BaseVAE, jrVAE, jVAE, rVAE
 from .imspec import ImSpec
 from .segmentor import Segmentor
 
-_OUT_OF_SCOPE = ("reg", "cls", "denoising_autoencoder")
+_OUT_OF_SCOPE = ("reg", "cls")
 
 
 def _read(filepath: str) -> Dict:
@@ -43,6 +46,8 @@ def load_model(filepath: str) -> Union[Segmentor, BaseVAE, Dict[str, torch.Tenso
             return load_vae_model(loaded)
         if model_type == "imspec":
             return load_imspec_model(loaded)
+        if model_type == "denoising_autoencoder":
+            return load_denoising_autoencoder(loaded)
     if model_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"model type '{model_type}' is outside the MI355X hot path of this build")
     raise ValueError("The model type {} cannot be loaded".format(model_type))
@@ -74,6 +79,26 @@ def load_imspec_model(meta_dict: Dict) -> Type[ImSpec]:
         meta_dict["batch_norm"] = meta_dict.pop("batchnorm")
     optimizer = meta_dict.pop("optimizer", None)
     model = ImSpec(in_dim, out_dim, latent_dim, **meta_dict)
+    model.net.load_state_dict(weights)
+    if optimizer is not None:
+        model.optimizer = optimizer
+    model.net.eval()
+    return model
+
+
+def load_denoising_autoencoder(meta_dict: Dict) -> Type[DenoisingAutoencoder]:
+    """DenoisingAutoencoder from {encoder_filters, decoder_filters, encoder_layers, decoder_layers, use_batch_norm,
+    upsampling_mode, weights, [optimizer]}, written here or by the reference; absent entries take the reference loader's
+    defaults (atomai/models/loaders.py:212-217: ``use_batch_norm`` True, unlike the constructor's False)."""
+    arch = dict(encoder_filters=meta_dict.pop("encoder_filters", [8, 16, 32, 64]),
+                decoder_filters=meta_dict.pop("decoder_filters", [64, 32, 16, 8]),
+                encoder_layers=meta_dict.pop("encoder_layers", [1, 2, 2, 2]),
+                decoder_layers=meta_dict.pop("decoder_layers", [2, 2, 2, 1]),
+                use_batch_norm=meta_dict.pop("use_batch_norm", True),
+                upsampling_mode=meta_dict.pop("upsampling_mode", "nearest"))
+    weights = meta_dict.pop("weights")
+    optimizer = meta_dict.pop("optimizer", None)
+    model = DenoisingAutoencoder(**arch, **meta_dict)
     model.net.load_state_dict(weights)
     if optimizer is not None:
         model.optimizer = optimizer
@@ -118,6 +143,9 @@ def load_ensemble(filepath: str) -> Tuple[Type[torch.nn.Module], Dict[int, Dict[
     elif model_type == "imspec":
         raise NotImplementedError("ImSpec ensembles are outside the MI355X hot path of this build "
                                   "(single ImSpec models load with load_model)")
+    elif model_type == "denoising_autoencoder":
+        raise NotImplementedError("denoiser ensembles are outside the MI355X hot path of this build "
+                                  "(single DenoisingAutoencoder models load with load_model)")
     elif model_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"model type '{model_type}' is outside the MI355X hot path of this build")
     else:

@@ -159,9 +159,12 @@ class BaseTrainer:
                and tar.shape[0] == feat.shape[0] and tar.shape[-2:] == feat.shape[2:]
                and ((tar.dtype == torch.int64 and tar.ndim == 3 and tcrit is losses_metrics.losses.dice_loss)
                     or (tar.dtype == torch.float32 and tar.ndim == 4 and tar.shape[1] == 1)))
-        if FUSE_LOSS and not self.compute_accuracy and (ce or bce or alt) and hasattr(self.net, "forward_loss"):
+        # MSELoss (mean) against a float target of the input's shape (N,1,H,W): the denoiser's head (nets/denoiser.py)
+        mse = (tcrit is losses_metrics.losses.MSELoss and self.criterion.reduction == "mean" and feat.ndim == 4
+               and tar.dtype == torch.float32 and tar.shape == feat.shape and tar.shape[1] == 1)
+        if FUSE_LOSS and not self.compute_accuracy and (ce or bce or alt or mse) and hasattr(self.net, "forward_loss"):
             # head + loss + their backward in one pass over the last activation (nets/fcnn.py: forward_loss); the same values
-            kind, out = self.net.forward_loss(feat, tar, **({"criterion": self.criterion} if alt else {}))
+            kind, out = self.net.forward_loss(feat, tar, **({"criterion": self.criterion} if (alt or mse) else {}))
             loss = out if kind == "loss" else self.criterion(out, tar)
         else:
             prob = self.net(feat)

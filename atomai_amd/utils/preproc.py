@@ -148,6 +148,28 @@ def init_imspec_dataloaders(X_train, y_train, X_test, y_test, batch_size: int, m
     return (*init_dataloaders(*tensors, batch_size, memory_alloc), dims)
 
 
+def preprocess_denoiser_data(X_train, y_train, X_test, y_test):
+    """Noisy / clean image pairs for the denoising autoencoder as float32 tensors (n, 1, h, w)
+    (atomai/utils/preproc.py:698-758): numpy arrays or torch tensors, all of one kind; a stack without the channel axis
+    gains one, with a warning; a noisy stack and its clean stack must agree in shape."""
+    data = (X_train, y_train, X_test, y_test)
+    all_np = all(isinstance(i, np.ndarray) for i in data)
+    all_t = all(isinstance(i, torch.Tensor) for i in data)
+    if not all_np and not all_t:
+        raise TypeError("Provide training and test data in the form of numpy arrays or torch tensors")
+    out = []
+    for a, what in zip(data, ("noisy training", "clean training", "noisy test", "clean test")):
+        if a.ndim == 3:
+            warnings.warn(f"Adding channel dimension of 1 to {what} images", UserWarning)
+            a = a[:, None]
+        out.append((torch.from_numpy(a) if all_np else a).float())
+    if out[0].shape != out[1].shape:
+        raise ValueError("Noisy and clean training images must have the same shape")
+    if out[2].shape != out[3].shape:
+        raise ValueError("Noisy and clean test images must have the same shape")
+    return tuple(out)
+
+
 def torch_format_spectra(spectra: np.ndarray, norm: bool = False) -> torch.Tensor:
     """(n, l) -> float32 (n, 1, l); optional global min-max normalisation over the WHOLE stack
     (atomai/utils/preproc.py:828-854)."""

@@ -352,6 +352,15 @@ int amx_px_bce_sum(const float* a, const float* scale, const float* shift, const
 int amx_px_focal_train(const float* a, const float* scale, const float* shift, const float* w, const float* b,
                        const float* target_f, const float* dfdc, float* dxn, float* part, float* partb, float* bstats,
                        float* lpart, int N, int H, int W, int C, int Cs, int rows, int rows_pix, void* stream);
+/* The tail of a DenoisingAutoencoder training step (atomai/models/denoiser.py: the decoder ends in Conv2d(C, 1, 1), the
+ * criterion is MSELoss) in ONE pass over the last activation: p = w . (a * scale + shift) + b in registers, loss term
+ * (p - t)^2 against target_f float [N][1][H][W], g = 2 (p - t) / npix, and from g what amx_px_bwd emits (dxn with padding
+ * channels 0, part [rows][Cs], partb [rows], bstats [rows][2][Cs] or NULL) for an upstream gradient of 1, plus lpart
+ * [rows] (amx_reduce_rows with 1 / npix gives the mean).  One output channel only; amx_px_ce_train_supported(Cs, 1);
+ * rows = amx_rows_for(npix), rows_pix = amx_rows_pix(npix).  No floating-point atomics. */
+int amx_px_mse_train(const float* a, const float* scale, const float* shift, const float* w, const float* b,
+                     const float* target_f, float* dxn, float* part, float* partb, float* bstats, float* lpart, int N,
+                     int H, int W, int C, int Cs, int rows, int rows_pix, void* stream);
 /* IoU of SegTrainer.accuracy_fn (trainers/trainer.py:727-737 -> losses_metrics/metrics.py:16-95): per-image K x K
  * confusion counts of (label, thresholded softmax / sigmoid class map) in one pass over the NCHW logits, replacing the
  * reference's host round trip (cv2.threshold per image + squeeze_channels + torch.bincount).  Exactly one of truth_i64

@@ -1,5 +1,5 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) — one JSON line each, written to gpurun_out/.
-   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec
+   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec|denoiser [--unfused-head]
 """
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -686,11 +686,98 @@ def bench_imspec(reps=3, iters=20, steps=10, warmup=4, emit=True):
     return out
 
 
+def bench_denoiser(hw=256, bs=32, steps=100, warmup=10, reps=5, fused_head=True, emit=True):
+    """DenoisingAutoencoder training step (default architecture [8, 16, 32, 64] / [64, 32, 16, 8], bs x hw x hw, fp32, MSE):
+    steps per second, and the fused 1x1-head + MSE tail (amx_px_mse_train) against the three-launch tail (amx_px_fwd ->
+    amx_mse_fwd_bwd -> amx_px_bwd), interleaved in ONE process on ONE model: warm-up of both paths, then an A/A pass (the
+    fused step against itself: `reps` rounds of `steps` steps per label, device-synchronised around each window) whose
+    largest difference between the two labels' rounds is the run-to-run spread, then the A/B pass in the same form.
+    ``fused_head=False`` (command line: --unfused-head) makes the three-launch tail the headline and skips the A/B."""
+    import atomai_amd.engine as eng
+    import atomai_amd.trainers.trainer as tr
+    rs = np.random.RandomState(0)
+    clean = rs.rand(bs, 1, hw, hw).astype(np.float32)
+    noisy = (clean + 0.1 * rs.randn(bs, 1, hw, hw)).astype(np.float32)
+    m = aoi.models.DenoisingAutoencoder(seed=1)
+    m.compile_trainer(aoi.utils.preprocess_denoiser_data(noisy, clean, noisy, clean), loss="mse", training_cycles=1,
+                      batch_size=bs, plot_training_history=False)
+    kinds = []
+    orig = type(m.net).forward_loss
+
+    def spy(self, *a, **k):
+        r = orig(self, *a, **k)
+        kinds.append(r[0])
+        return r
+    type(m.net).forward_loss = spy
+
+    mse_default = eng.FUSE_PX_MSE
+
+    def step(fused):
+        tr.FUSE_LOSS = eng.FUSE_PX_LOSS = eng.FUSE_PX_MSE = fused
+        try:
+            return m.train_step(m.X_train[0], m.y_train[0])[0]
+        finally:
+            tr.FUSE_LOSS = eng.FUSE_PX_LOSS = True
+            eng.FUSE_PX_MSE = mse_default
+
+    def rounds(labels):
+        t = {name: [] for name, _ in labels}
+        for _ in range(reps):
+            for name, fused in labels:
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                for _ in range(steps):
+                    step(fused)
+                torch.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) / steps * 1e3)
+        return t
+    try:
+        for fused in (True, False):
+            for _ in range(warmup):
+                step(fused)
+        assert kinds == ["loss"] * warmup, kinds               # the fused node ran; the unfused step never asks for it
+        lines = []
+        if not fused_head:
+            t = rounds([("unfused", False)])
+            aa = ab = None
+        else:
+            aa = rounds([("fused_a", True), ("fused_b", True)])
+            ab = rounds([("fused", True), ("unfused", False)])
+            t = ab
+        for tt in (aa, ab) if fused_head else (t,):
+            for name, v in tt.items():
+                lines.append(f"{name:<10} step ms {[f'{u:.3f}' for u in v]}  median {np.median(v):.3f}  min {min(v):.3f}")
+    finally:
+        type(m.net).forward_loss = orig
+    head = "fused" if fused_head else "unfused"
+    ms = float(np.median(t[head]))
+    out = {"metric": f"DenoisingAutoencoder training step, default architecture, {hw}x{hw}, bs={bs}, {head} head",
+           "unit": "steps/s", "value": round(1e3 / ms, 2), "higher_is_better": True, "ms_per_step": round(ms, 3),
+           "detail": {k: [round(u, 3) for u in v] for k, v in t.items()}}
+    if fused_head:
+        spread = max(abs(a - b) for a, b in zip(aa["fused_a"], aa["fused_b"]))
+        spread = max(spread, max(aa["fused_a"]) - min(aa["fused_a"]), max(aa["fused_b"]) - min(aa["fused_b"]))
+        out.update({"aa_spread_ms": round(spread, 3), "aa": {k: [round(u, 3) for u in v] for k, v in aa.items()},
+                    "unfused_ms_per_step": round(float(np.median(ab["unfused"])), 3),
+                    "fused_minus_unfused_ms": round(ms - float(np.median(ab["unfused"])), 3)})
+        lines.append(f"A/A spread {spread:.3f} ms; fused {ms:.3f} ms, unfused {np.median(ab['unfused']):.3f} ms per step")
+    out["log"] = [f"# python tools/bench_extra.py denoiser{'' if fused_head else ' --unfused-head'} - default architecture, "
+                  f"bs {bs} {hw}^2, interleaved in one process, {reps} x {steps} steps per label"] + lines
+    if emit:
+        print("\n".join(out["log"]))
+        print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["rvae", "predict"]
+    unfused_head = "--unfused-head" in what            # denoiser: time the three-launch tail instead of the fused head
+    what = [w for w in what if w != "--unfused-head"]
     os.makedirs("gpurun_out", exist_ok=True)
     res = {}
     for w in what:
+        if w == "denoiser":
+            res[w] = bench_denoiser(fused_head=not unfused_head)
+            continue
         res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)
