@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from ..nets.fcnn import _HipNet, predict_proba
-from .locator import Locator, locate_device
+from .locator import Locator, check_d, locate_device, warn_default_d
 from .. import _lib as L
 from ..utils import (get_downsample_factor, get_nb_classes, img_pad, img_resize, set_train_rng, torch_format_image,
                      torch_format_spectra)
@@ -49,14 +49,15 @@ class BasePredictor:
 
     def batch_predict(self, data: torch.Tensor, out_shape: Tuple[int], num_batches: int,
                       on_chunk=None) -> torch.Tensor:
-        """Batch-by-batch prediction into a host tensor (predictor.py:82-106).  ``on_chunk(start, out)`` sees
-        each chunk's output while it is still on the model's device."""
+        """Batch-by-batch prediction into a host tensor (predictor.py:82-106).  ``on_chunk(start, out, x)`` sees
+        each chunk's output, and the input chunk it came from, while they are still on the model's device."""
         bs = max(1, len(data) // max(1, num_batches))
         out = torch.empty(out_shape)
         for i in range(0, len(data), bs):
-            res = self.forward_(data[i:i + bs])
+            x = data[i:i + bs].to(self.device)
+            res = self.forward_(x)
             if on_chunk is not None:
-                on_chunk(i, res)
+                on_chunk(i, res, x)
             out[i:i + bs] = res.cpu()
         return out
 
@@ -175,6 +176,19 @@ class SegPredictor(BasePredictor):
             prob = torch.exp(prob)
         return prob.permute(0, 2, 3, 1)
 
+    def input_frames(self, chunk: torch.Tensor) -> torch.Tensor:
+        """(m, H, W) float32 frames of an uploaded (m, 1, H, W) input chunk as the reference's ``predict(...,
+        return_image=True)`` returns them: where ``preprocess`` left the min-max normalisation to the first-layer
+        kernel, it is applied here (`amx_sub_div`, the same two fp32 operations)."""
+        raw = chunk.contiguous()
+        norm = getattr(self, "_norm", None)
+        if norm is not None:
+            frames = torch.empty_like(raw)
+            L.call("amx_sub_div", L.ptr(raw), L.ptr(frames), raw.numel(), float(norm[0]), float(norm[1]),
+                   L.stream_ptr(raw))
+            raw = frames
+        return raw[:, 0]
+
     def batch_predict(self, data: torch.Tensor, out_shape: Tuple[int], num_batches: int,
                       on_chunk=None) -> torch.Tensor:
         if not (torch.cuda.is_available() and str(self.device).startswith("cuda")):
@@ -212,7 +226,7 @@ class SegPredictor(BasePredictor):
             st = stage[k]
             if on_chunk is not None:
                 st["done"].synchronize()
-                on_chunk(st["s"], st["prob"])
+                on_chunk(st["s"], st["prob"], st["d"])
             prob = st["prob"] = st["prob"].contiguous()
             copy_out.wait_event(st["done"])
             L.call("amx_copy16", L.ptr(prob), ctypes.c_void_p(pin_out[k % NS].data_ptr()), prob.numel() * 4, 128,
@@ -403,21 +417,26 @@ class SegPredictor(BasePredictor):
 
     def run(self, image_data: np.ndarray, compute_coords=True, **kwargs: int):
         """Prediction (+ blob centres).  With ``compute_coords`` the Locator kernels run on each chunk's
-        probabilities while they are still on the device (predictor.py:262-298 runs a host loop afterwards)."""
+        probabilities while they are still on the device (predictor.py:262-298 runs a host loop afterwards); with
+        ``refine`` the centres are then fitted (``amx_peak_refine``) to the chunk's preprocessed input frames, which
+        are still resident as well."""
         start_time = time.time()
         if not compute_coords:
             return self.predict(image_data, **kwargs)       # the reference prints nothing on this branch
         if self.refine:
-            raise NotImplementedError("peak refinement (per-atom scipy.optimize Gaussian fits) is outside the "
-                                      "MI355X hot path of this build")
+            if kwargs.get("distributed", False):
+                raise NotImplementedError("refine=True is not available with distributed=True")
+            check_d(self.d)
+            warn_default_d(self.d)
         thresh = kwargs.get("thresh", self.thresh)
         dist_edge = Locator(thresh).dist_edge               # Locator's default, as the reference uses it
         coordinates = {}
 
-        def on_chunk(start, prob):
-            for i, v in locate_device(prob, thresh, dist_edge).items():
+        def on_chunk(start, prob, x):
+            frames = self.input_frames(x) if self.refine else None
+            for i, v in locate_device(prob, thresh, dist_edge, frames, self.d, start).items():
                 coordinates[start + i] = v
-        kw = {k: v for k, v in kwargs.items() if k != "thresh"}
+        kw = {k: v for k, v in kwargs.items() if k not in ("thresh", "d")}
         decoded = self.predict(image_data, _on_chunk=on_chunk, **kw)
         if kwargs.get("distributed", False) and self._dist_world()[1] > 1:
             # frame indices seen by on_chunk are local to this rank's range: shift, then merge on rank 0

@@ -576,6 +576,20 @@ int amx_locate_label(const float* prob, int B, int H, int W, int C, int nch, flo
 int amx_locate_emit(const void* work, int B, int H, int W, int nch, int dist_edge, double* coords, int* meta,
                     long cap, void* stream);
 
+/* ---- Peak refinement (atomai/utils/coords.py:179-231 peak_refinement, 152-176 gaussian_2d): every atom of the flat
+ *      table that amx_locate_emit writes — coords (n,2) fp64 (row, col), meta (n,2) int32 (frame, class), rows sorted
+ *      by frame — is replaced by the centre of a rotated 2-D Gaussian fitted (Levenberg-Marquardt, fp64, analytic
+ *      Jacobian, at most 200 Jacobian evaluations) to the 2d x 2d patch of its fp32 frame (B,H,W) around the rounded
+ *      (half to even) start, d = d[frame] with 2 <= d <= dmax <= 32.  out (n,2) fp64; status (n) int32:
+ *      0 fitted, 1 kept: patch leaves the frame, 2 kept: centre moved 3 px or more, 3 kept: no convergence,
+ *      4 kept: frame index or d[frame] out of range.  Kept rows are copied bit for bit.
+ *      amx_nn2_quarter_mean writes the reference's default half-side (coords.py:205-207) per frame:
+ *      d[f] = int(mean(distances to the two nearest other atoms, over the atoms of frame f) * 0.25), 0 for a frame
+ *      with fewer than 3 atoms. */
+int amx_peak_refine(const float* frames, int B, int H, int W, const double* coords, const int* meta, const int* d,
+                    int dmax, long n, double* out, int* status, void* stream);
+int amx_nn2_quarter_mean(const double* coords, const int* meta, long n, int B, int* d, void* stream);
+
 /* ---- torch.optim.Adam defaults as one flat launch (trainer.py:539, vitrainer.py:218).  b1, b2 and the bias
  * corrections bc1 = 1-b1^t, bc2 = 1-b2^t are DOUBLES: torch forms 1-beta in double before rounding to fp32
  * (1 - float(0.999) is off by 1.3e-5 relative, a systematic error in every second moment). */

@@ -768,6 +768,124 @@ def bench_denoiser(hw=256, bs=32, steps=100, warmup=10, reps=5, fused_head=True,
     return out
 
 
+def _refine_frames(rs, frames, hw, spacing, sigma):
+    """Synthetic frames with a jittered square lattice of Gaussian atoms, their true centres, and atom masks."""
+    grid = np.arange(spacing, hw - spacing + 1, spacing, dtype=np.float64)
+    r = 3 * int(np.ceil(sigma)) + 1
+    yy, xx = np.mgrid[-r:r + 1, -r:r + 1]
+    disc = (yy[r - 2:r + 3, r - 2:r + 3] ** 2 + xx[r - 2:r + 3, r - 2:r + 3] ** 2 <= 5).astype(np.int64)
+    imgs = np.full((frames, hw, hw), 0.1)
+    masks = np.zeros((frames, hw, hw), dtype=np.int64)
+    centres = []
+    for f in range(frames):
+        cr = (grid[:, None] + rs.uniform(-1.5, 1.5, (len(grid), len(grid)))).ravel()
+        cc = (grid[None, :] + rs.uniform(-1.5, 1.5, (len(grid), len(grid)))).ravel()
+        for a, b in zip(cr, cc):
+            ia, ib = int(round(a)), int(round(b))
+            imgs[f, ia - r:ia + r + 1, ib - r:ib + r + 1] += rs.uniform(0.6, 1.0) * np.exp(
+                -((yy + ia - a) ** 2 + (xx + ib - b) ** 2) / (2 * sigma ** 2))
+            masks[f, ia - 2:ia + 3, ib - 2:ib + 3] |= disc
+        centres.append(np.stack((cr, cc), 1))
+    imgs += 0.02 * rs.randn(frames, hw, hw)
+    return imgs.astype(np.float32), centres, masks
+
+
+def bench_refine(frames=4, hw=1024, spacing=16, d=4, sigma=1.6, cycles=300, sample=200, reps=5, emit=True):
+    """Gaussian peak refinement on `frames` synthetic hw x hw frames that carry a lattice of (hw / spacing - 1)^2 Gaussian
+    atoms each: (a) amx_peak_refine alone on the true centres displaced by up to 0.7 px (event-timed), (b)
+    SegPredictor.run(refine=True, d) end to end with a default U-Net trained for `cycles` steps on crops of the same
+    frames, next to the same run with refine=False, and (c) the yardstick: the reference's host loop, one
+    scipy.optimize.curve_fit per atom (atomai/utils/coords.py:208-228), over a sample of the atoms of (a)."""
+    from scipy import optimize
+    from atomai_amd.predictors import SegPredictor
+    from atomai_amd.predictors.locator import refine_device
+    from atomai_amd.utils import gaussian_2d
+    rs = np.random.RandomState(0)
+    imgs, centres, masks = _refine_frames(rs, frames, hw, spacing, sigma)
+    start = [c + rs.uniform(-0.7, 0.7, c.shape) for c in centres]
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    fr = torch.from_numpy(imgs).to(dev)
+    xy = torch.from_numpy(np.concatenate(start)).to(dev)
+    meta = np.zeros((len(xy), 2), dtype=np.int32)
+    meta[:, 0] = np.repeat(np.arange(frames), [len(c) for c in start])
+    meta = torch.from_numpy(meta).to(dev)
+    n = len(xy)
+    recs = timed_calls({"amx_peak_refine"}) if dev == "cuda" else []
+    for _ in range(2):
+        out, status = refine_device(fr, xy, meta, d, return_status=True)
+    recs.clear()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        out, status = refine_device(fr, xy, meta, d, return_status=True)
+    if dev == "cuda":
+        torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / reps
+    ms = [e0.elapsed_time(e1) for _, e0, e1 in recs] or [wall * 1e3]
+    out, status = out.cpu().numpy(), status.cpu().numpy()
+    truth = np.concatenate(centres)
+    err0, err1 = np.abs(xy.cpu().numpy() - truth).max(1), np.abs(out - truth).max(1)
+    # (c) the host yardstick on a sample of the same atoms; everything it reads is on the host before the clock starts
+    pick = rs.permutation(n)[:sample]
+    grid = tuple(np.indices((2 * d, 2 * d)))
+    starts_h, frame_h = xy.cpu().numpy(), meta.cpu().numpy()[:, 0]
+    host = starts_h[pick].copy()                             # an atom whose fit fails or strays keeps its start
+    t0 = time.perf_counter()
+    for k, i in enumerate(pick):
+        corner = np.rint(starts_h[i]).astype(np.int64) - d   # half to even, as the kernel rounds
+        window = imgs[frame_h[i], corner[0]:corner[0] + 2 * d, corner[1]:corner[1] + 2 * d]
+        guess = np.array([window[d, d], d, d, 1.0, 1.0, 0.0, 0.0])
+        try:
+            fit = optimize.curve_fit(gaussian_2d, grid, window.ravel(), p0=guess)[0]
+        except RuntimeError:                                 # scipy: no convergence within maxfev
+            continue
+        if np.hypot(fit[1] - d, fit[2] - d) < 3:
+            host[k] = fit[1:3] + corner
+    host_dt = (time.perf_counter() - t0) / len(pick)
+    # (b) end to end
+    m = aoi.models.Segmentor(nb_classes=1, seed=1)
+    crop = min(256, hw)
+    rs2 = np.random.RandomState(1)
+    idx = [(f % frames, *rs2.randint(0, hw - crop + 1, 2)) for f in range(16)]
+    X = np.stack([imgs[f, i:i + crop, j:j + crop] for f, i, j in idx])[:, None]
+    Y = np.stack([masks[f, i:i + crop, j:j + crop] for f, i, j in idx])[:, None].astype(np.float32)
+    m.fit(X, Y, X[:8], Y[:8], training_cycles=cycles, batch_size=8, plot_training_history=False, print_loss=10 ** 9)
+    e2e = {}
+    for refine in (False, True):
+        p = SegPredictor(m.net, refine=refine, use_gpu=True, d=d, nb_classes=1, verbose=False)
+        p.run(imgs)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            dec, co = p.run(imgs)
+        e2e[refine] = ((time.perf_counter() - t0) / reps, co)
+    found = sum(len(v) for v in e2e[True][1].values())
+    moved = sum(int((e2e[True][1][i][:, :2] != e2e[False][1][i][:, :2]).any(1).sum()) for i in e2e[True][1])
+    res = {"metric": f"amx_peak_refine atoms/sec ({frames} frames of {hw}x{hw}, {n} atoms, d={d})",
+           "value": round(n / (float(np.median(ms)) * 1e-3), 1), "unit": "atoms/s", "n_gpus": 1, "dtype": "fp64",
+           "ms_kernel": [round(v, 3) for v in ms], "ms_call_wall": round(wall * 1e3, 3),
+           "status_counts": np.bincount(status, minlength=5).tolist(),
+           "max_abs_error_vs_truth_px": {"start": round(float(err0.max()), 3),
+                                          "refined_median": round(float(np.median(err1)), 4),
+                                          "refined_max": round(float(err1.max()), 3)},
+           "max_abs_diff_vs_host_loop_px": float(np.abs(host - out[pick]).max()),
+           "end_to_end": {"atoms_found": found, "atoms_moved_by_fit": moved, "train_cycles": cycles,
+                          "s_per_run_refine": round(e2e[True][0], 4), "s_per_run_plain": round(e2e[False][0], 4),
+                          "atoms_per_s": round(found / e2e[True][0], 1),
+                          "frames_per_s": round(frames / e2e[True][0], 2)},
+           "cpu_baseline": {"value": round(1 / host_dt, 1), "unit": "atoms/s", "cores": 1, "kind": "reference loop",
+                            "sample": f"{len(pick)} atoms through scipy.optimize.curve_fit, same run"}}
+    res["log"] = [f"# python tools/bench_extra.py refine - {frames} frames of {hw}^2, {n} atoms, d = {d}",
+                  f"amx_peak_refine alone        {res['value']:>14.1f} atoms/s  (kernel ms {res['ms_kernel']}, status counts "
+                  f"fitted / patch / gate / no convergence / bad row {res['status_counts']})",
+                  f"SegPredictor.run(refine=True){res['end_to_end']['atoms_per_s']:>14.1f} atoms/s  ({found} atoms found, {moved} "
+                  f"moved; {e2e[True][0]:.4f} s per run against {e2e[False][0]:.4f} s with refine=False)",
+                  f"host loop of curve_fit       {res['cpu_baseline']['value']:>14.1f} atoms/s  ({len(pick)} atoms of the same "
+                  f"table; largest |device - host| {res['max_abs_diff_vs_host_loop_px']:.2e} px)"]
+    if emit:
+        print("\n".join(res["log"]))
+        print(json.dumps(res), flush=True)
+    return res
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["rvae", "predict"]
     unfused_head = "--unfused-head" in what            # denoiser: time the three-launch tail instead of the fused head
@@ -778,6 +896,6 @@ if __name__ == "__main__":
         if w == "denoiser":
             res[w] = bench_denoiser(fused_head=not unfused_head)
             continue
-        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
+        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)
