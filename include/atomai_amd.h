@@ -638,6 +638,33 @@ int amx_avgpool_fwd(const float* x, float* y, int N, int H, int W, int kh, int k
 int amx_mse_rows(long n);
 int amx_mse_fwd_bwd(const float* p, const float* t, float* grad, float* part, long n, int rows, void* stream);
 
+/* ---- stat: Gaussian-mixture EM / k-means over a stack of flattened sub-images (atomai/stat/multivar.py:110-172,
+ * imlocal.gmm = sklearn.mixture.GaussianMixture with 'diag' or 'spherical' covariance), csrc/stat.hip.
+ * amx_gmm_pass: one E step and the sums of the M step over X [N][D] fp32, K <= 32 components, any D >= 1.
+ *   mean, prec [K][D] fp32; cst [K] fp64 = log weight + 1/2 sum_d log prec - D/2 log 2 pi; row n, component k:
+ *   logp = cst_k - 1/2 sum_d (x_d - mean_kd)^2 prec_kd (direct difference form, in fp64 from the fp32 operands),
+ *   lse_n = log sum_k exp logp, r_nk = exp(logp - lse_n) (hard != 0: one-hot on the arg-max = a Lloyd step of k-means
+ *   when prec = 1 and the cst are equal), label_n = arg-max (first on ties).
+ *   Workgroup g owns rows [g R, (g + 1) R), R = amx_gmm_rows(), G = ceil(N / R) workgroups, and writes its partial rows
+ *   Pn [G][K] fp64 (sum r), Pl [G] fp64 (sum lse), Pc [G] int32 (labels that differ from prev_label; 0 if that is NULL)
+ *   and, unless P1 == P2 == NULL, P1, P2 [G][K][D] fp32 = r^T (X - shift), r^T (X - shift)^2 (fp32 MFMA, chains of R
+ *   <= 1024 rows; shift [D] = the column mean keeps var = S2/n - (S1/n)^2 well conditioned).
+ *   Optional (NULL = not wanted): logp [N][K] fp64, label [N] int32.
+ * amx_gmm_reduce: adds the partial rows in workgroup order in fp64 -> S1, S2 [K][D] (both or neither), nk [K], *lse_sum,
+ *   *changed (each optional).  No floating-point atomics: two runs give the same bits.
+ * amx_gmm_finalize: the M step in fp64: n = nk + 10 DBL_EPSILON; mean = S1/n + shift; var = max(S2/n - (S1/n)^2, 0) +
+ *   reg_covar, or (spherical != 0) its mean over D; prec = 1 / var; weights = n / N; mean32 / prec32 / cst: the next pass's
+ *   inputs (cst from the fp32-rounded precisions).  mean / var / prec (fp64) all or none. */
+long amx_gmm_rows(void);
+int amx_gmm_pass(const float* X, long N, int D, int K, const float* mean, const float* prec, const double* cst,
+                 const float* shift, int hard, const int* prev_label, float* P1, float* P2, double* Pn, double* Pl, int* Pc,
+                 double* logp, int* label, void* stream);
+int amx_gmm_reduce(const float* P1, const float* P2, const double* Pn, const double* Pl, const int* Pc, long G, int K, int D,
+                   double* S1, double* S2, double* nk, double* lse_sum, long* changed, void* stream);
+int amx_gmm_finalize(const double* nk, const double* S1, const double* S2, const float* shift, int K, int D, double N,
+                     double reg_covar, int spherical, double* mean, double* var, double* prec, float* mean32, float* prec32,
+                     double* weights, double* cst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,59 @@
+"""`gpu` tier for atomai_amd.stat through libatomai_amd.so on the MI355X."""
+import pytest
+
+import _stat_checks as K
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("shape", K.PASS_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_pass_against_fp64(shape):
+    K.check_pass(shape, "cuda")
+
+
+def test_update_against_fp64():
+    K.check_update("cuda")
+
+
+def test_determinism():
+    K.check_determinism("cuda")
+
+
+def test_convergence_warning():
+    K.check_no_convergence_warning("cuda")
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+@pytest.mark.parametrize("cov", ["diag", "spherical"])
+@pytest.mark.parametrize("name", K.CASES)
+def test_gmm_partition(name, cov, seed):
+    K.check_gmm(name, cov, seed)
+
+
+@pytest.mark.parametrize("name", K.CASES)
+def test_pca(name):
+    K.check_pca(name)
+
+
+def test_pca_gram_over_features():
+    K.check_pca_wide("cuda")
+
+
+def test_pca_gmm():
+    K.check_pca_gmm()
+
+
+def test_host_logic():
+    K.check_host_logic()
+
+
+def test_transition_matrix():
+    K.check_transition_matrix()
+
+
+def test_update_classes():
+    K.check_update_classes()
+
+
+def test_edges():
+    K.check_edges("cuda")

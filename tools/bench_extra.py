@@ -1,5 +1,5 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) — one JSON line each, written to gpurun_out/.
-   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec|denoiser [--unfused-head]
+   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec|denoiser|stat [--unfused-head]
 """
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -886,6 +886,112 @@ def bench_refine(frames=4, hw=1024, spacing=16, d=4, sigma=1.6, cycles=300, samp
     return res
 
 
+def bench_stat(frames=20, per_frame=1000, r=32, C=3, classes=10, noise=0.05, n_pca=4, em_iters=20, emit=True):
+    """stat.imlocal on a synthetic stack of frames * per_frame windows of r x r x C (D = r r C) cut from frames that carry
+    `classes` planted prototypes + noise: gmm(n_components=classes) and pca(n_pca) end to end, the EM pass kernel alone
+    (event-timed; GB/s against the N D 4 bytes of the stack, which one pass must read at least once), and — if
+    scikit-learn imports here — the reference-equivalent GaussianMixture(...).fit_predict on the same array in the same
+    run."""
+    rs = np.random.default_rng(0)
+    side = int(np.ceil(np.sqrt(per_frame)))
+    H = (side + 2) * r
+    proto = rs.uniform(0.1, 0.9, (classes, r, r, C)).astype(np.float32)
+    imgs = rs.uniform(0, 0.05, (frames, H, H, C)).astype(np.float32)
+    coords, planted = {}, []
+    for b in range(frames):
+        rows = []
+        for n in range(per_frame):
+            i, j = r + r * (n // side), r + r * (n % side)
+            k = int(rs.integers(classes))
+            imgs[b, i - r // 2:i - r // 2 + r, j - r // 2:j - r // 2 + r] = \
+                proto[k] + noise * rs.standard_normal((r, r, C), dtype=np.float32)
+            rows.append((i, j, 0.0))
+            planted.append(k)
+        coords[b] = np.array(rows, dtype=np.float64)
+    planted = np.array(planted)
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    from atomai_amd.stat import _gmm
+    import warnings
+    _gmm.pass_timings = []
+    try:
+        s = aoi.stat.imlocal(imgs, coords, r, 0)
+        N, D = s.d0, s.d1 * s.d2 * s.d3
+        t0 = time.perf_counter()
+        X = s._device_stack()
+        if dev == "cuda":
+            torch.cuda.synchronize()
+        t_up = time.perf_counter() - t0
+        s.gmm(2)                                          # warm-up: library load, allocator, first launches
+        _gmm.pass_timings.clear()
+        t0 = time.perf_counter()
+        cla, cl_all, cf = s.gmm(classes)
+        t_gmm = time.perf_counter() - t0
+        runs = list(_gmm.pass_timings)
+        s.pca(1)
+        t0 = time.perf_counter()
+        comp, proj, _ = s.pca(n_pca)
+        t_pca = time.perf_counter() - t0
+        # the pass alone: a fit that is not allowed to stop, so that the median is over em_iters EM passes
+        _gmm.pass_timings.clear()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", _gmm.ConvergenceWarning)
+            _gmm.fit_gmm(X, classes, "diag", 1, tol=0.0, max_iter=em_iters)
+        if dev == "cuda":
+            torch.cuda.synchronize()
+        ms = {kind: [e0.elapsed_time(e1) for k, K, e0, e1 in _gmm.pass_timings if k == kind and K == classes]
+              for kind in ("em", "lloyd")}
+    finally:
+        _gmm.pass_timings = None
+
+    def purity(labels):
+        return float(sum(np.bincount(planted[labels == c]).max() for c in np.unique(labels)) / len(labels))
+    ours = cf[:, 2].astype(np.int64)
+    n_run = {kind: sum(1 for k, K, _, _ in runs if k == kind and K == classes) for kind in ("em", "lloyd")}
+    n_run["other"] = len(runs) - n_run["em"] - n_run["lloyd"]
+    gb = N * D * 4 / 1e9
+    med = {k: (float(np.median(v)) if v else None) for k, v in ms.items()}
+    res = {"metric": f"stat.imlocal.gmm EM pass ({N} windows of {r}x{r}x{C}, D={D}, K={classes})",
+           "value": None if med["em"] is None else round(med["em"], 3), "unit": "ms/pass", "n_gpus": 1, "dtype": "fp32 in, fp64 E step",
+           "gb_per_s_vs_stack_bytes": None if med["em"] is None else round(gb / (med["em"] * 1e-3), 1),
+           "stack_mb": round(gb * 1e3, 1), "em_passes": n_run["em"], "lloyd_passes": n_run["lloyd"],
+           "em_passes_timed": len(ms["em"]),
+           "ms_lloyd_pass": None if med["lloyd"] is None else round(med["lloyd"], 3), "other_passes": n_run["other"],
+           "s_upload": round(t_up, 3), "s_gmm_end_to_end": round(t_gmm, 3), "s_pca_end_to_end": round(t_pca, 3),
+           "purity_vs_planted": round(purity(ours), 4), "classes_found": int(ours.max())}
+    log = [f"# python tools/bench_extra.py stat - {N} windows of {r}x{r}x{C} (D = {D}), {classes} planted classes, noise {noise}",
+           f"upload of the fp32 stack ({res['stack_mb']} MB)      {t_up:8.3f} s",
+           f"imlocal.gmm({classes}) end to end          {t_gmm:8.3f} s  ({res['lloyd_passes']} Lloyd + {res['em_passes']} EM passes "
+           f"+ {res['other_passes']} seeding / label passes; purity against the planted classes {res['purity_vs_planted']})",
+           f"imlocal.pca({n_pca}) end to end           {t_pca:8.3f} s"]
+    if med["em"] is not None:
+        log.append(f"amx_gmm_pass, EM (soft, K = {classes})   {med['em']:8.3f} ms/pass = {res['gb_per_s_vs_stack_bytes']} GB/s "
+                   f"against N D 4 bytes (median of {len(ms['em'])} passes of a fit with tol = 0); Lloyd (hard) "
+                   f"{med['lloyd']:.3f} ms/pass")
+    try:
+        from sklearn.mixture import GaussianMixture
+    except ImportError:
+        GaussianMixture = None
+    if GaussianMixture is None:
+        res["cpu_baseline"] = None
+        log.append("scikit-learn does not import here: device figures alone")
+    else:
+        X = s.imgstack.reshape(N, D)
+        t0 = time.perf_counter()
+        clf = GaussianMixture(n_components=classes, covariance_type="diag", random_state=1)
+        ref = clf.fit_predict(X)
+        t_ref = time.perf_counter() - t0
+        res["cpu_baseline"] = {"value": round(t_ref, 3), "unit": "s", "kind": "sklearn GaussianMixture.fit_predict, same array, "
+                               "same run", "n_iter": int(clf.n_iter_), "purity_vs_planted": round(purity(ref), 4),
+                               "threads": int(os.environ.get("OMP_NUM_THREADS", 0)) or None}
+        log.append(f"sklearn GaussianMixture({classes}, 'diag').fit_predict on the host, same array: {t_ref:8.3f} s "
+                   f"({clf.n_iter_} EM iterations, purity {res['cpu_baseline']['purity_vs_planted']})")
+    res["log"] = log
+    if emit:
+        print("\n".join(log))
+        print(json.dumps(res), flush=True)
+    return res
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["rvae", "predict"]
     unfused_head = "--unfused-head" in what            # denoiser: time the three-launch tail instead of the fused head
@@ -896,6 +1002,6 @@ if __name__ == "__main__":
         if w == "denoiser":
             res[w] = bench_denoiser(fused_head=not unfused_head)
             continue
-        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
+        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "stat": bench_stat, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)
