@@ -1,7 +1,8 @@
-"""Coordinate grids for the rVAE spatial decoder (reference: atomai/utils/coords.py:37-83) and the Gaussian peak
-refinement of atom positions (coords.py:152-231)."""
+"""Coordinate grids for the rVAE spatial decoder (reference: atomai/utils/coords.py:37-83), the Gaussian peak
+refinement of atom positions (coords.py:152-231) and the nearest-neighbour analysis of atom tables (coords.py:86-149,
+234-301, 350-400, 475-537) on the kernels of csrc/knn.hip."""
 import warnings
-from typing import Optional, Tuple, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -76,3 +77,224 @@ def peak_refinement(imgdata: np.ndarray, coordinates: np.ndarray, d: Optional[in
     meta = torch.zeros((n, 2), dtype=torch.int32, device=device)
     out = refine_device(frames, xy, meta, d)
     return np.concatenate((out.cpu().numpy(), cls), axis=-1)
+
+
+# ------------------------------------------------------------------------------------------ nearest-neighbour analysis
+def _device():
+    from .. import _lib as L
+    return "cuda" if torch.cuda.is_available() and not L.is_test_backend() else "cpu"
+
+
+def _to_device(a, dtype=np.float64):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(_device())
+
+
+def _tables(coordinates) -> List[np.ndarray]:
+    """The frames' tables in dictionary order; a single array is one frame."""
+    if isinstance(coordinates, np.ndarray):
+        coordinates = {0: coordinates}
+    tables = [np.asarray(t) for t in coordinates.values()]
+    for t in tables:
+        if t.ndim != 2 or t.shape[1] < 2:
+            raise ValueError("expected (N, >=2) tables of coordinates [row, col, class, ...]")
+    return tables
+
+
+def _nn_tables(tables: List[np.ndarray], nn: int, upper_bound: Optional[float]):
+    """get_nn_distances_ for every table, all of them through ONE launch of ``amx_knn``: the tables are concatenated
+    into one flat table and every frame is a segment."""
+    from . import _knn
+    k = int(nn) + 1
+    if int(nn) != nn or not 2 <= k <= _knn.K_MAX:
+        raise ValueError(f"nn + 1 = {nn + 1} neighbours per atom (the atom itself is one) must lie between 2 and "
+                         f"{_knn.K_MAX}, the limit of the device kernel")
+    bound = np.inf if upper_bound is None else float(upper_bound)
+    offs = np.concatenate(([0], np.cumsum([len(t) for t in tables]))).astype(np.int64)
+    if offs[-1] > 0:
+        flat = _to_device(np.concatenate([t[:, :2] for t in tables], axis=0))
+        dist, idx = (a.cpu().numpy() for a in _knn.knn(flat, flat, k, bound, offs, offs))
+    else:
+        dist, idx = np.empty((0, k)), np.empty((0, k), dtype=np.int64)
+    distances, pairs = [], []
+    for t, lo, hi in zip(tables, offs[:-1], offs[1:]):
+        d, ix = dist[lo:hi], idx[lo:hi] - lo
+        keep = ~np.isinf(d).any(axis=1)                 # a row with any missing neighbour is dropped
+        distances.append(d[keep, 1:])
+        pairs.append(t[ix[keep]])
+    return distances, pairs
+
+
+def get_nn_distances_(coordinates: np.ndarray, nn: int = 2,
+                      upper_bound: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Distances of every atom of one frame to its ``nn`` nearest neighbours (coords.py:86-113): an (atoms' x nn) array
+    of distances and the (atoms' x (nn+1) x columns) coordinates of the atom and its neighbours.  ``upper_bound`` is
+    cKDTree's ``distance_upper_bound`` (only ``distance < upper_bound`` counts); atoms with fewer than ``nn`` such
+    neighbours are dropped, so a table with fewer than ``nn + 1`` atoms gives empty arrays.  ``nn + 1 <= 32``."""
+    d, p = _nn_tables(_tables(np.asarray(coordinates)), nn, upper_bound)
+    return d[0], p[0]
+
+
+def get_nn_distances(coordinates: Union[Dict[int, np.ndarray], np.ndarray], nn: int = 2,
+                     upper_bound: Optional[float] = None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+    """``get_nn_distances_`` for a dictionary of frames (coords.py:116-149), all frames in one launch.  Returns the two
+    lists in dictionary order."""
+    return _nn_tables(_tables(coordinates), nn, upper_bound)
+
+
+def _pyplot():
+    try:
+        import matplotlib.pyplot as plt
+    except ImportError as e:
+        raise ImportError("plot_results=True needs matplotlib, which does not import here; "
+                          "call with plot_results=False") from e
+    return plt
+
+
+def _plot_bonds(distances, pairs, distance_ideal, frame, **kwargs):
+    """One figure per frame: every atom-neighbour bond as a line coloured by its deviation from ``distance_ideal``."""
+    from matplotlib.collections import LineCollection
+    plt = _pyplot()
+    fig, ax = plt.subplots(figsize=(8, 8))
+    if len(distances):
+        centre = np.repeat(pairs[:, :1, :2], pairs.shape[1] - 1, axis=1)
+        seg = np.stack((centre, pairs[:, 1:, :2]), axis=2).reshape(-1, 2, 2)[..., ::-1]      # (x, y) = (col, row)
+        lines = LineCollection(seg, cmap="bwr", linewidths=1.5)
+        lines.set_array(distances.reshape(-1) - distance_ideal)
+        ax.add_collection(lines)
+        fig.colorbar(lines, ax=ax, label="bond length - ideal (px)")
+        ax.scatter(pairs[:, 0, 1], pairs[:, 0, 0], s=4, c="k")
+    if kwargs.get("h") is not None and kwargs.get("w") is not None:
+        ax.set_xlim(0, kwargs["w"])
+        ax.set_ylim(kwargs["h"], 0)
+    else:
+        ax.autoscale()
+        ax.invert_yaxis()
+    ax.set_aspect("equal")
+    ax.set_title(f"frame {frame}")
+    if kwargs.get("savedir") is not None:
+        import os
+        fig.savefig(os.path.join(kwargs["savedir"], f"frame_{frame}.png"))
+    plt.show()
+
+
+def map_bonds(coordinates: Dict[int, np.ndarray], nn: int = 2, upper_bound: Optional[float] = None,
+              distance_ideal: Optional[float] = None, plot_results: bool = True, **kwargs) -> np.ndarray:
+    """Nearest-neighbour bond lengths of every frame (coords.py:475-515), concatenated; with ``plot_results`` one bond
+    map per frame, coloured by the deviation from ``distance_ideal`` (default: the mean).  Keywords ``h``, ``w`` (frame
+    size) and ``savedir``."""
+    distances, pairs = get_nn_distances(coordinates, nn, upper_bound)
+    out = np.concatenate(distances)
+    if plot_results:
+        if distance_ideal is None:
+            distance_ideal = np.mean(out)
+        for i, (d, p) in enumerate(zip(distances, pairs)):
+            _plot_bonds(d, p, distance_ideal, i, **kwargs)
+    return out
+
+
+def compare_coordinates(coordinates1: np.ndarray, coordinates2: np.ndarray, d_max: float, plot_results: bool = False,
+                        **kwargs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Matches every row of ``coordinates1`` (predicted) to its nearest row of ``coordinates2`` (true) and keeps the
+    pairs with ``distance < d_max`` (coords.py:266-301).  As in the reference the distance is taken over ALL columns
+    of the tables (the class column takes part), so both need the same 2 or 3 columns.  Returns the matched rows of
+    both tables and their distances.  For plotting pass the image as ``expdata`` (and ``fsize``)."""
+    from . import _knn
+    c1, c2 = np.asarray(coordinates1, dtype=np.float64), np.asarray(coordinates2, dtype=np.float64)
+    if c1.ndim != 2 or c2.ndim != 2 or c1.shape[1] != c2.shape[1]:
+        raise ValueError("expected two (N, dim) tables with the same number of columns")
+    if c2.shape[1] not in _knn.DIMS:
+        raise ValueError(f"the device neighbour search handles dim 2 or 3, got {c2.shape[1]} columns")
+    if len(c1) and len(c2):
+        dist, idx = (a.cpu().numpy()[:, 0] for a in _knn.knn(_to_device(c2), _to_device(c1), 1))
+    else:
+        dist, idx = np.full(len(c1), np.inf), np.full(len(c1), -1, dtype=np.int64)
+    keep = dist < d_max
+    m1, m2, delta_r = c1[keep], c2[idx[keep]], dist[keep]
+    if plot_results:
+        expdata = kwargs.get("expdata")
+        if expdata is None:
+            raise AssertionError("For plotting, provide 2D image via 'expdata' keyword")
+        plt = _pyplot()
+        fsize = kwargs.get("fsize", 20)
+        plt.figure(figsize=(int(fsize * 1.25), fsize))
+        plt.imshow(expdata, cmap="gray")
+        im = plt.scatter(m1[:, 1], m1[:, 0], c=delta_r, cmap="jet", s=5)
+        plt.colorbar(im).set_label("Position deviation (px)")
+        plt.show()
+    return m1, m2, delta_r
+
+
+def find_coord_clusters(coord_class_dict_1, coord_class_dict_2, rmax: float):
+    """For every atom of ``coord_class_dict_1[0]`` collects the atoms of ALL frames of ``coord_class_dict_2`` (keys
+    0 .. len - 1, or a list) whose (row, col) lies within ``distance < rmax`` (coords.py:350-400).  Returns the
+    clusters' means and standard deviations over (row, col), (n, 2) each, and the list of clusters, every one a table
+    ordered by distance.  An atom without a neighbour gives an empty cluster and NaN."""
+    from . import _knn
+    frames = [np.asarray(coord_class_dict_2[k], dtype=np.float64) for k in range(len(coord_class_dict_2))]
+    every = np.concatenate(frames, axis=0) if frames else np.empty((0, 3))
+    c0 = np.asarray(coord_class_dict_1[0], dtype=np.float64)[:, :2]
+    if len(c0):
+        count, idx, _ = (a.cpu().numpy() for a in _knn.radius(_to_device(every[:, :2]), _to_device(c0), float(rmax)))
+    else:
+        count, idx = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    clusters = [every[ix] for ix in np.split(idx, np.cumsum(count)[:-1])] if len(c0) else []
+    nan = np.full(2, np.nan)
+    means = [c[:, :2].mean(axis=0) if len(c) else nan for c in clusters]
+    stds = [c[:, :2].std(axis=0) if len(c) else nan for c in clusters]
+    return np.array(means).reshape(-1, 2), np.array(stds).reshape(-1, 2), clusters
+
+
+def _frame2d(img) -> np.ndarray:
+    img = np.asarray(img)
+    if img.ndim == 3 and img.shape[-1] == 1:
+        img = img[..., 0]
+    if img.ndim != 2:
+        raise ValueError(f"expected a 2-D frame or (H, W, 1), got shape {img.shape}")
+    return img
+
+
+def _intensities(tables, frames, r):
+    """Mean window intensity for every atom of every table, one launch of ``amx_window_mean`` for all of them."""
+    from . import _knn
+    if int(r) != r or int(r) < 1:
+        raise ValueError(f"the window side r must be a positive integer, got {r}")
+    tables = [np.asarray(t, dtype=np.float64) for t in tables]
+    tables = [t if t.size else np.empty((0, 2)) for t in tables]
+    if any(t.ndim != 2 or t.shape[1] < 2 for t in tables):
+        raise ValueError("expected (N, >=2) tables of coordinates [row, col, ...]")
+    frames = [_frame2d(f) for f in frames]
+    counts = [len(t) for t in tables]
+    if sum(counts) == 0:
+        return [np.empty(0) for _ in tables]
+    if len({f.shape for f in frames}) != 1:
+        raise ValueError("all frames must have the same shape")
+    meta = np.zeros((sum(counts), 2), dtype=np.int32)
+    meta[:, 0] = np.repeat(np.arange(len(tables)), counts)
+    xy = np.concatenate([t[:, :2] for t in tables], axis=0)
+    out = _knn.window_mean(_to_device(np.stack(frames), np.float32), _to_device(xy), _to_device(meta, np.int32), int(r))
+    return np.split(out.cpu().numpy(), np.cumsum(counts)[:-1])
+
+
+def get_intensities_(coordinates: np.ndarray, img: np.ndarray, r: int = 3) -> np.ndarray:
+    """Mean intensity of ``img`` (2-D, or (H, W, 1)) in the window of side ``r`` around every rounded atom position
+    (coords.py:234-252), as float64 means of the float32 frame.  Odd ``r``: [c - r//2, c + r//2 + 1); even ``r``:
+    [c - r//2, c + r//2).  numpy's slicing rules: a window cut by the high edge averages what is left, one that starts
+    below 0 is an empty slice, NaN."""
+    return _intensities([coordinates], [img], r)[0]
+
+
+def get_intensities(coordinates_all: Dict[int, np.ndarray], nn_input, r: int = 3) -> List[np.ndarray]:
+    """``get_intensities_`` for every frame of the dictionary (coords.py:255-263), frame ``k`` of ``nn_input`` for key
+    ``k``, all atoms of all frames in one launch."""
+    keys = list(coordinates_all.keys())
+    return _intensities([coordinates_all[k] for k in keys], [nn_input[k] for k in keys], r)
+
+
+def remove_edge_coord(coordinates: np.ndarray, dim: Tuple[int, int], dist_edge: int) -> np.ndarray:
+    """Drops the rows closer than ``dist_edge`` to the frame's edges, with the reference's comparison as written
+    (coords.py:518-537): column 0 against ``w`` and column 1 against ``h`` of ``dim = (h, w)``."""
+    coordinates = np.asarray(coordinates)
+    h, w = dim
+    c0, c1 = coordinates[:, 0], coordinates[:, 1]
+    edge = (c0 > w - dist_edge) | (c0 < dist_edge) | (c1 > h - dist_edge) | (c1 < dist_edge)
+    return coordinates[~edge]

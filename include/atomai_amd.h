@@ -665,6 +665,33 @@ int amx_gmm_finalize(const double* nk, const double* S1, const double* S2, const
                      double reg_covar, int spherical, double* mean, double* var, double* prec, float* mean32, float* prec32,
                      double* weights, double* cst, void* stream);
 
+/* ---- nearest-neighbour analysis of atom tables (atomai/utils/coords.py: get_nn_distances, compare_coordinates,
+ * find_coord_clusters, get_intensities), csrc/knn.hip.  All fp64, no atomics: two runs give the same bits.
+ * amx_knn: segmented brute-force k nearest neighbours.  pts [P][dim], qry [Q][dim] fp64, dim 2 or 3; S segments given by
+ *   the int64 offsets pseg [S+1] into pts and qseg [S+1] into qry: a query of segment s searches the points of segment s
+ *   only.  tiles [T][2] int64 = (segment, first query row) of every tile of at most 256 consecutive queries of one
+ *   segment (one workgroup each; a row that does not lie in its segment is skipped).  1 <= k <= 32.  Writes dist [Q][k]
+ *   ascending and idx [Q][k] int64 (a row of pts); a slot without a neighbour holds +inf and -1.  The distance is the sqrt
+ *   of the fp64 sum of squared differences (added in coordinate order); candidates are ranked by that sum, equal sums by
+ *   the smaller row.  A point counts only if dist < bound, strictly (+inf: no bound).  A query that is itself one of
+ *   the points is NOT excluded.  Q == 0, S == 0 or T == 0: returns 0 without a launch.  Queries no tile covers are not
+ *   written.
+ * amx_radius_count: count [Q] int64 = number of rows of pts [P][dim] with dist < rmax, per query.
+ * amx_radius_emit: with offs [Q] = the exclusive prefix sum of count and M = its total, writes for query i the rows
+ *   (idx), distances (dist) and i itself (qid) of those points to [offs[i], offs[i] + count[i]), in row order; nothing
+ *   is written at or beyond M.
+ * amx_window_mean: out [n] fp64 = mean of the fp32 frame meta[2 i] of frames (B,H,W) over the window of side r around
+ *   (rint(row), rint(col)) of coords (n,2) fp64 (rint: half to even); meta (n,2) int32 as for amx_peak_refine.  Window
+ *   [c - r/2, c + r/2 + 1) for odd r, [c - r/2, c + r/2) for even r, clipped at the high edges (the mean is over what is
+ *   left); NaN when a window starts below 0, is empty, or the frame index is out of range.  1 <= r <= 1024. */
+int amx_knn(const double* pts, long P, const double* qry, long Q, int dim, const long* pseg, const long* qseg, int S,
+            const long* tiles, long T, int k, double bound, double* dist, long* idx, void* stream);
+int amx_radius_count(const double* pts, long P, const double* qry, long Q, int dim, double rmax, long* count, void* stream);
+int amx_radius_emit(const double* pts, long P, const double* qry, long Q, int dim, double rmax, const long* offs, long M,
+                    long* qid, long* idx, double* dist, void* stream);
+int amx_window_mean(const float* frames, int B, int H, int W, const double* coords, const int* meta, long n, int r,
+                    double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

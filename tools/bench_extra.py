@@ -1,5 +1,5 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) — one JSON line each, written to gpurun_out/.
-   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec|denoiser|stat [--unfused-head]
+   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec|denoiser|stat|knn [--unfused-head]
 """
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -992,6 +992,115 @@ def bench_stat(frames=20, per_frame=1000, r=32, C=3, classes=10, noise=0.05, n_p
     return res
 
 
+def bench_knn(frames=64, per_frame=4000, nn=6, r=3, hw=512, reps=20, emit=True):
+    """Nearest-neighbour analysis of a Locator dictionary: get_nn_distances and get_intensities end to end (host tables
+    in, host arrays out), amx_knn alone (device events), and the reference's per-frame cKDTree loop where scipy imports."""
+    from atomai_amd.utils import _knn
+    rng = np.random.default_rng(0)
+    side = int(np.ceil(np.sqrt(per_frame)))
+    ij = np.stack(np.meshgrid(np.arange(side), np.arange(side), indexing="ij"), -1).reshape(-1, 2)[:per_frame]
+    coords = {}
+    for f in range(frames):
+        xy = 7.0 * ij + 8.0 + rng.uniform(-0.8, 0.8, (per_frame, 2))
+        coords[f] = np.concatenate((xy, np.zeros((per_frame, 1))), axis=1)
+    assert max(t[:, :2].max() for t in coords.values()) < hw - 2
+    imgs = rng.uniform(0, 1, (frames, hw, hw)).astype(np.float32)
+    k, N = nn + 1, frames * per_frame
+
+    def wall(fn, n=3):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)), out
+    aoi.utils.get_nn_distances({0: coords[0]}, nn)                                  # warm-up: library load, allocator
+    t_nn, (dists, pairs) = wall(lambda: aoi.utils.get_nn_distances(coords, nn))
+    t_int, ints = wall(lambda: aoi.utils.get_intensities(coords, imgs, r))
+    flat = torch.from_numpy(np.concatenate([t[:, :2] for t in coords.values()])).cuda()
+    offs = np.arange(frames + 1, dtype=np.int64) * per_frame
+
+    def kernel_ms(pts, seg):
+        """amx_knn alone: tables and outputs made beforehand, device events around the one launch."""
+        tiles = _knn.tile_table(seg)
+        seg_d, tiles_d = torch.from_numpy(seg).cuda(), torch.from_numpy(tiles).cuda()
+        dist = torch.empty(len(pts), k, dtype=torch.float64, device="cuda")
+        idx = torch.empty(len(pts), k, dtype=torch.int64, device="cuda")
+        out = []
+        for i in range(reps + 2):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            L.call("amx_knn", L.ptr(pts), len(pts), L.ptr(pts), len(pts), 2, L.ptr(seg_d), L.ptr(seg_d), len(seg) - 1,
+                   L.ptr(tiles_d), len(tiles), k, float("inf"), L.ptr(dist), L.ptr(idx), L.stream_ptr(pts))
+            e1.record()
+            torch.cuda.synchronize()
+            if i >= 2:
+                out.append(e0.elapsed_time(e1))
+        return out
+    ms = kernel_ms(flat, offs)
+    med = float(np.median(ms))
+    pairs_eval = frames * per_frame ** 2
+    flops = 5.0 * pairs_eval                          # two differences, two squares, one addition per pair (dim 2), fp64
+    mb_in, mb_out = N * 2 * 8 / 1e6, N * k * 16 / 1e6
+    one = torch.from_numpy(coords[0][:, :2].copy()).cuda()
+    med1 = float(np.median(kernel_ms(one, np.array([0, per_frame], dtype=np.int64))))
+    res = {"metric": f"amx_knn, k = {k}, {frames} frames x {per_frame} atoms in one launch (brute force, fp64)",
+           "value": round(med, 3), "unit": "ms", "n_gpus": 1, "dtype": "fp64", "reps": reps,
+           "pair_evaluations": pairs_eval, "tflops_fp64_at_5_per_pair": round(flops / (med * 1e-3) / 1e12, 2),
+           "mb_in": round(mb_in, 1), "mb_out": round(mb_out, 1), "ms_one_frame_alone": round(med1, 3),
+           "s_get_nn_distances": round(t_nn, 4), "s_get_intensities": round(t_int, 4)}
+    log = [f"# python tools/bench_extra.py knn - {frames} frames x {per_frame} jittered-lattice atoms (spacing 7), nn = {nn}, "
+           f"r = {r}, frames {hw} x {hw} float32",
+           f"get_nn_distances(nn={nn}), host dictionary in, host lists out   {t_nn:8.4f} s (median of 3; one launch for "
+           f"all frames, {sum(len(d) for d in dists)} rows kept)",
+           f"get_intensities(r={r}), host arrays in (upload of {imgs.nbytes / 1e6:.0f} MB included), host lists out "
+           f"{t_int:8.4f} s (median of 3)",
+           f"amx_knn alone (one launch, tables resident), k = {k}               {med:8.3f} ms (median of {reps}, device events, "
+           f"min {min(ms):.3f} max {max(ms):.3f})",
+           f"   = {pairs_eval:.3e} pair evaluations (the search is O(n^2) per frame), {flops / (med * 1e-3) / 1e12:.2f} TFLOP/s fp64 "
+           f"at 5 flops per pair; {mb_in:.1f} MB read once from HBM, {mb_out:.1f} MB written",
+           f"amx_knn, one frame of {per_frame} atoms alone                      {med1:8.3f} ms (median of {reps})"]
+    try:
+        from scipy import spatial
+    except ImportError:
+        spatial = None
+    if spatial is None:
+        res["cpu_baseline"] = None
+        log.append("scipy does not import here: the per-frame cKDTree loop was NOT measured")
+    else:
+        def ref_nn():
+            out = []
+            for t in coords.values():
+                d, i = spatial.cKDTree(t[:, :2]).query(t[:, :2], k=k)
+                out.append((d[:, 1:], t[i]))
+            return out
+
+        def ref_int():
+            out = []
+            for f, t in coords.items():
+                img = imgs[f]
+                out.append(np.array([np.mean(img[int(np.around(c[0])) - r // 2:int(np.around(c[0])) + r // 2 + 1,
+                                                 int(np.around(c[1])) - r // 2:int(np.around(c[1])) + r // 2 + 1])
+                                     for c in t]))
+            return out
+        t0 = time.perf_counter(); rn = ref_nn(); t_rn = time.perf_counter() - t0
+        t0 = time.perf_counter(); ri = ref_int(); t_ri = time.perf_counter() - t0
+        same = all(np.array_equal(a[1], b) for a, b in zip(rn, pairs))
+        err = max(float(np.abs(a[0] - b).max()) for a, b in zip(rn, dists))
+        res["cpu_baseline"] = {"s_ckdtree_loop": round(t_rn, 4), "s_intensity_loop": round(t_ri, 4), "same_neighbours": same,
+                               "max_abs_distance_difference": err}
+        log.append(f"host, same frames, same run: one scipy cKDTree per frame, query k = {k}        {t_rn:8.4f} s "
+                   f"(neighbours identical: {same}, max |distance difference| {err:.1e})")
+        log.append(f"host, same frames, same run: per-atom numpy window mean loop            {t_ri:8.4f} s")
+    res["log"] = log
+    if emit:
+        print("\n".join(log))
+        print(json.dumps(res), flush=True)
+    return res
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["rvae", "predict"]
     unfused_head = "--unfused-head" in what            # denoiser: time the three-launch tail instead of the fused head
@@ -1002,6 +1111,6 @@ if __name__ == "__main__":
         if w == "denoiser":
             res[w] = bench_denoiser(fused_head=not unfused_head)
             continue
-        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "stat": bench_stat, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
+        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "stat": bench_stat, "knn": bench_knn, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)
