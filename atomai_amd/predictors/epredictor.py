@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 from ..nets.fcnn import _HipNet, predict_proba
-from ..utils import get_downsample_factor, torch_format_image
+from ..utils import cluster_coord as _cluster_coord
+from ..utils import cluster_coord_frames, get_downsample_factor, torch_format_image
 from .locator import Locator
 from .predictor import BasePredictor
 
@@ -118,30 +119,21 @@ class EnsemblePredictor(BasePredictor):
 
 
 def cluster_coord(coord_class_dict, eps: float, min_samples: int = 10) -> Tuple[np.ndarray]:
-    """DBSCAN clustering of coordinates collapsed over the members (atomai/utils/coords.py:304-347)."""
-    from sklearn import cluster
-    coordinates_all = np.empty((0, 3))
-    for k in range(len(coord_class_dict)):
-        coordinates_all = np.append(coordinates_all, coord_class_dict[k], axis=0)
-    labels = cluster.DBSCAN(eps=eps, min_samples=min_samples).fit(coordinates_all[:, :2]).labels_
-    clusters, clusters_var, clusters_mean = [], [], []
-    for lab in np.unique(labels)[1:]:
-        coord = coordinates_all[np.where(labels == lab)]
-        clusters.append(coord)
-        clusters_mean.append(np.mean(coord[:, :2], axis=0))
-        clusters_var.append(np.var(coord[:, :2], axis=0))
-    return np.array(clusters, dtype=object), np.array(clusters_mean), np.array(clusters_var)
+    """DBSCAN clustering of coordinates collapsed over the members (atomai/utils/coords.py:304-347), on the device:
+    ``atomai_amd.utils.cluster_coord``."""
+    return _cluster_coord(coord_class_dict, eps, min_samples)
 
 
 def ensemble_locate(nn_output_ensemble: np.ndarray, **kwargs) -> Tuple[Dict, Dict]:
     """Mean and variance of every detected coordinate over the members' predictions (5D input:
-    members x frames x H x W x C); epredictor.py:297-330."""
+    members x frames x H x W x C); epredictor.py:297-330.  The Locator runs over the whole members x frames stack and
+    the members' centres of all frames are clustered in one segmented pass, every frame a segment."""
     eps = kwargs.get("eps", 0.5)
     thresh = kwargs.get("threshold", 0.5)
-    loc = Locator(thresh)
-    coord_mean_all, coord_var_all = {}, {}
-    for i in range(nn_output_ensemble.shape[1]):
-        members = loc.run(np.ascontiguousarray(nn_output_ensemble[:, i], dtype=np.float32))   # one launch set
-        _, coord_mean, coord_var = cluster_coord(members, eps)
-        coord_mean_all[i], coord_var_all[i] = coord_mean, coord_var
-    return coord_mean_all, coord_var_all
+    nn_output_ensemble = np.asarray(nn_output_ensemble)
+    if nn_output_ensemble.ndim != 5:
+        raise ValueError("expected a 5D array: members x frames x H x W x C")
+    M, F = nn_output_ensemble.shape[:2]
+    tables = Locator(thresh).run(nn_output_ensemble.reshape(M * F, *nn_output_ensemble.shape[2:]))
+    means, variances = cluster_coord_frames([[tables[m * F + i] for m in range(M)] for i in range(F)], eps)
+    return dict(enumerate(means)), dict(enumerate(variances))

@@ -1,6 +1,6 @@
-from .coords import (compare_coordinates, find_coord_clusters, gaussian_2d, get_intensities, get_intensities_,
-                     get_nn_distances, get_nn_distances_, grid2xy, imcoordgrid, map_bonds, peak_refinement,
-                     remove_edge_coord, transform_coordinates)
+from .coords import (cluster_coord, cluster_coord_frames, compare_coordinates, find_coord_clusters, gaussian_2d,
+                     get_intensities, get_intensities_, get_nn_distances, get_nn_distances_, grid2xy, imcoordgrid,
+                     map_bonds, peak_refinement, remove_edge_coord, transform_coordinates)
 from .img import crop_borders, extract_subimages, get_coord_grid, get_imgstack, img_pad, img_resize
 from .nn import (Hook, average_weights, get_downsample_factor, get_nb_classes, gpu_usage_map, mock_forward,
                  reset_bnorm, sample_weights, set_train_rng, weights_init)

@@ -244,6 +244,63 @@ def find_coord_clusters(coord_class_dict_1, coord_class_dict_2, rmax: float):
     return np.array(means).reshape(-1, 2), np.array(stds).reshape(-1, 2), clusters
 
 
+def _cluster_segments(tables: List[np.ndarray], eps: float, min_samples: int, members: bool = True):
+    """DBSCAN of every table of ``tables`` on its own, all of them through ONE segmented pass of csrc/cluster.hip.
+    Returns one (clusters, mean, var) per table as ``cluster_coord`` does; ``clusters`` is None unless ``members``."""
+    from . import _cluster
+    tables = [np.asarray(t, dtype=np.float64) for t in tables]
+    for t in tables:
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("expected (N, 3) tables of coordinates [row, col, class]")
+    sizes = np.array([len(t) for t in tables], dtype=np.int64)
+    offs = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    flat = np.concatenate(tables, axis=0) if len(tables) else np.empty((0, 3))
+    pts = _to_device(flat[:, :2])
+    r = _cluster._run(pts, eps, min_samples, offs)
+    kseg, count, mean, var, rows, moff = _cluster.cluster_stats(pts, r["labels"], r["rank"], r["seg"])
+    count, mean, var = count.cpu().numpy(), mean.cpu().numpy(), var.cpu().numpy()
+    if members:
+        rows, moff = rows.cpu().numpy(), moff.cpu().numpy()
+    placed = np.concatenate(([0], np.cumsum(count)))
+    out = []
+    for s in range(len(tables)):
+        k0, k1 = int(kseg[s]), int(kseg[s + 1])
+        # the reference takes np.unique(labels)[1:], which assumes the first label is DBSCAN's noise label -1: a table
+        # without noise loses its cluster 0 instead (kept on purpose)
+        if placed[k1] - placed[k0] == sizes[s]:
+            k0 = min(k0 + 1, k1)
+        clusters = [flat[rows[moff[k]:moff[k + 1]]] for k in range(k0, k1)] if members else None
+        # (the reference's np.array of an empty list has shape (0,))
+        none = np.array([])
+        out.append((clusters, mean[k0:k1].copy() if k1 > k0 else none, var[k0:k1].copy() if k1 > k0 else none.copy()))
+    return out
+
+
+def cluster_coord(coord_class_dict: Union[Dict[int, np.ndarray], List[np.ndarray]], eps: float,
+                  min_samples: int = 10) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Collapses the (N, 3) tables of a stack (keys 0 .. len - 1, or a list) onto the xy plane and clusters them with
+    DBSCAN (coords.py:304-347; ``sklearn.cluster.DBSCAN(eps, min_samples)`` there, csrc/cluster.hip here, with the same
+    labels).  Returns the member rows of every cluster (an object array of (m, 3) tables, rows in stack order), the
+    clusters' means and their population variances over (row, col).  As in the reference the first of the sorted labels
+    is skipped: the noise, or cluster 0 when there is no noise."""
+    frames = [np.asarray(coord_class_dict[k], dtype=np.float64) for k in range(len(coord_class_dict))]
+    every = np.concatenate(frames, axis=0) if frames else np.empty((0, 3))
+    clusters, mean, var = _cluster_segments([every], eps, min_samples)[0]
+    return np.array(clusters, dtype=object), mean, var
+
+
+def cluster_coord_frames(stacks, eps: float, min_samples: int = 10) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+    """``cluster_coord`` for many stacks at once: ``stacks[i]`` is a dictionary or list of (N, 3) tables (the members'
+    detections of frame i, say).  Every stack is one segment of a single pass.  Returns the list of the stacks' cluster
+    means and the list of their variances."""
+    every = []
+    for st in stacks:
+        frames = [np.asarray(st[k], dtype=np.float64) for k in range(len(st))]
+        every.append(np.concatenate(frames, axis=0) if frames else np.empty((0, 3)))
+    res = _cluster_segments(every, eps, min_samples, members=False)
+    return [m for _, m, _ in res], [v for _, _, v in res]
+
+
 def _frame2d(img) -> np.ndarray:
     img = np.asarray(img)
     if img.ndim == 3 and img.shape[-1] == 1:

@@ -692,6 +692,51 @@ int amx_radius_emit(const double* pts, long P, const double* qry, long Q, int di
 int amx_window_mean(const float* frames, int B, int H, int W, const double* coords, const int* meta, long n, int r,
                     double* out, void* stream);
 
+/* ---- density clustering of atom tables (atomai/utils/coords.py: cluster_coord = sklearn.cluster.DBSCAN over the xy
+ * columns), csrc/cluster.hip.  Segmented DBSCAN in fp64 on a cell grid: pts [N][2] fp64, N < 2^31, S segments given by
+ * the int64 offsets seg [S+1] (the layout of amx_knn); points of different segments never see one another.  Integer
+ * atomics (min, or) only, on values whose final state does not depend on the order: two runs give the same bits.
+ * Two points are neighbours if dx*dx + dy*dy <= eps2 in fp64, evaluated in that order without contraction; a point is
+ * its own neighbour.  The caller sorts the points by `key` (stable) between amx_cluster_keys and the rest: spts, ssid,
+ * skey are pts, sid, key in that order, orig [N] int64 the original row of every sorted position, and cstart [C+1]
+ * int64 the first sorted position of every cell (cstart[c] = number of keys < c).
+ * amx_cluster_grid: per segment (one workgroup each) the bounding box and the cell edge h = max(heps, W/n, H/n,
+ *   sqrt(W H / n)) for a W x H box of n points, so that the segment has at most 3 n + 1 cells whatever W / eps is;
+ *   heps must exceed eps by the margin derived in cluster.hip.  Writes grid [S][3] fp64 = (xmin, ymin, h) and gdim
+ *   [S][2] int64 = (nx, ny).  cbase [S+1] int64: first cell of every segment; a segment whose grid would not fit
+ *   between cbase[s] and cbase[s+1] gets one cell (correct, only slower).
+ * amx_cluster_keys: key [N] int64 = cbase[s] + cy nx + cx and sid [N] int32 = s (key = cbase[S], sid = -1 for a row no
+ *   segment holds).
+ * amx_cluster_core: core [N] int32 (sorted order) = 1 if at least min_samples points of the 3 x 3 surrounding cells are
+ *   neighbours, else 0.
+ * amx_cluster_hook: one hooking round of the connected components of the core-core graph.  pin, pout [N] int32 are
+ *   indexed by ORIGINAL row and hold original rows; pin is read only and must be flat (pin[pin[i]] == pin[i]), pout must
+ *   equal pin on entry.  For every core-core edge with roots a < b: pout[b] = min(pout[b], a) and *changed |= 1.
+ * amx_cluster_jump: pointer jumping to the root, pb[i] = pa[i] = root of i in pb (in place; needs pb[i] <= i).
+ *   Start from parent[i] = i; alternate hook and jump until *changed stays 0: parent[i] of a core row is then the
+ *   smallest core row of its component.
+ * amx_cluster_label: rank [N+1] int64 = number of root rows (core and parent[i] == i) before row i.  label [N] int64
+ *   (original order) = rank[r] - rank[seg[s]] with r = parent[i] for a core row, the smallest parent among the core
+ *   neighbours for any other row, -1 if there is none: scikit-learn's numbering.
+ * amx_cluster_stats: K clusters; members [M] int64 = rows of pts, those of cluster k at [moff[k], moff[k+1]).  One thread
+ *   per cluster adds in member order: mean [K][2] = sum / m, then var [K][2] = sum (x - mean)^2 / m (two passes, the
+ *   population variance, as np.var); count [K] int64 = m.  An empty cluster gets NaN. */
+int amx_cluster_grid(const double* pts, long N, const long* seg, int S, const long* cbase, double heps, double* grid,
+                     long* gdim, void* stream);
+int amx_cluster_keys(const double* pts, long N, const long* seg, int S, const long* cbase, const double* grid,
+                     const long* gdim, long* key, int* sid, void* stream);
+int amx_cluster_core(const double* spts, long N, const int* ssid, const long* skey, int S, const long* cbase,
+                     const long* gdim, const long* cstart, long C, double eps2, long min_samples, int* core, void* stream);
+int amx_cluster_hook(const double* spts, long N, const int* ssid, const long* skey, int S, const long* cbase,
+                     const long* gdim, const long* cstart, long C, double eps2, const int* core, const long* orig,
+                     const int* pin, int* pout, int* changed, void* stream);
+int amx_cluster_jump(int* pa, int* pb, long N, void* stream);
+int amx_cluster_label(const double* spts, long N, const int* ssid, const long* skey, const long* seg, int S,
+                      const long* cbase, const long* gdim, const long* cstart, long C, double eps2, const int* core,
+                      const long* orig, const int* parent, const long* rank, long* label, void* stream);
+int amx_cluster_stats(const double* pts, long N, const long* members, long M, const long* moff, long K, long* count,
+                      double* mean, double* var, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

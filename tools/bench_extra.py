@@ -1101,6 +1101,83 @@ def bench_knn(frames=64, per_frame=4000, nn=6, r=3, hw=512, reps=20, emit=True):
     return res
 
 
+def bench_cluster(members=12, frames=64, per_frame=4000, sigma=0.15, eps=0.5, min_samples=10, reps=20, emit=True):
+    """Density clustering of an ensemble's detections: every frame holds ``members`` jittered copies of one lattice of
+    ``per_frame`` atoms.  The segmented DBSCAN alone (device table in, device labels out), the clustering of
+    ensemble_locate end to end (host tables in, host means and variances out), and scikit-learn's DBSCAN frame by frame
+    on the host where it imports, with the labels compared."""
+    from atomai_amd.utils import _cluster
+    rng = np.random.default_rng(0)
+    side = int(np.ceil(np.sqrt(per_frame)))
+    ij = np.stack(np.meshgrid(np.arange(side), np.arange(side), indexing="ij"), -1).reshape(-1, 2)[:per_frame]
+    stacks = []
+    for f in range(frames):
+        base = 7.0 * ij + 8.0 + rng.uniform(-0.8, 0.8, (per_frame, 2))
+        stacks.append([np.concatenate((base + rng.normal(0.0, sigma, base.shape), np.zeros((per_frame, 1))), axis=1)
+                       for _ in range(members)])
+    n_seg = members * per_frame
+    N = frames * n_seg
+    offs = np.arange(frames + 1, dtype=np.int64) * n_seg
+
+    def wall(fn, n):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return ts, out
+    flat = torch.from_numpy(np.concatenate([t[:, :2] for st in stacks for t in st])).cuda()
+    _cluster.dbscan(flat[:n_seg].contiguous(), eps, min_samples)                    # warm-up: library load, allocator
+    ts, (labels, core, rounds) = wall(lambda: _cluster.dbscan(flat, eps, min_samples, offs), reps)
+    med = float(np.median(ts))
+    ts1, _ = wall(lambda: _cluster.dbscan(flat[:n_seg].contiguous(), eps, min_samples), reps)
+    t_e2e, (means, variances) = wall(lambda: aoi.utils.cluster_coord_frames(stacks, eps, min_samples), 3)
+    t_e2e = float(np.median(t_e2e))
+    labels = labels.cpu().numpy()
+    res = {"metric": f"segmented DBSCAN, {frames} frames x {members} members x {per_frame} atoms in one pass (fp64, cell grid)",
+           "value": round(med * 1e3, 3), "unit": "ms", "n_gpus": 1, "dtype": "fp64", "reps": reps, "points": N,
+           "rounds": rounds, "clusters": int(sum(len(m) for m in means)), "noise_rows": int((labels < 0).sum()),
+           "ms_one_frame_alone": round(float(np.median(ts1)) * 1e3, 3), "s_cluster_coord_frames": round(t_e2e, 4)}
+    log = [f"# python tools/bench_extra.py cluster - {frames} frames x {members} members x {per_frame} jittered-lattice atoms "
+           f"(spacing 7, sigma = {sigma} px), eps = {eps}, min_samples = {min_samples}: {N} rows",
+           f"segmented DBSCAN alone (device table in, labels out, sorts and read-backs included)  {med * 1e3:9.3f} ms "
+           f"(median of {reps}, wall clock around a synchronised call, min {min(ts) * 1e3:.3f} max {max(ts) * 1e3:.3f}); "
+           f"{rounds} rounds of hooking",
+           f"segmented DBSCAN, one frame of {n_seg} rows alone                                      "
+           f"{float(np.median(ts1)) * 1e3:9.3f} ms (median of {reps})",
+           f"cluster_coord_frames, host tables in, host means and variances out                     {t_e2e:9.4f} s "
+           f"(median of 3; {res['clusters']} clusters kept, {res['noise_rows']} noise rows)"]
+    try:
+        from sklearn.cluster import DBSCAN
+    except ImportError:
+        DBSCAN = None
+    if DBSCAN is None:
+        res["cpu_baseline"] = None
+        log.append("scikit-learn does not import here: the per-frame DBSCAN on the host was NOT measured")
+    else:
+        t0 = time.perf_counter()
+        ref_means, same = [], True
+        for f, st in enumerate(stacks):                      # the host path of ensemble_locate before this kernel
+            every = np.empty((0, 3))
+            for t in st:
+                every = np.append(every, t, axis=0)
+            lab = DBSCAN(eps=eps, min_samples=min_samples).fit(every[:, :2]).labels_
+            ref_means.append(np.array([np.mean(every[lab == c, :2], axis=0) for c in np.unique(lab)[1:]]))
+            same = same and np.array_equal(lab, labels[offs[f]:offs[f + 1]])
+        t_ref = time.perf_counter() - t0
+        err = max(float(np.abs(a - b).max()) for a, b in zip(ref_means, means) if len(a))
+        res["cpu_baseline"] = {"s_sklearn_loop": round(t_ref, 4), "same_labels": bool(same), "max_abs_mean_difference": err}
+        log.append(f"host, same tables, same run: np.append + sklearn DBSCAN + per-label means, per frame  {t_ref:9.4f} s "
+                   f"(labels identical: {same}, max |mean difference| {err:.1e})")
+    res["log"] = log
+    if emit:
+        print("\n".join(log))
+        print(json.dumps(res), flush=True)
+    return res
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["rvae", "predict"]
     unfused_head = "--unfused-head" in what            # denoiser: time the three-launch tail instead of the fused head
@@ -1111,6 +1188,6 @@ if __name__ == "__main__":
         if w == "denoiser":
             res[w] = bench_denoiser(fused_head=not unfused_head)
             continue
-        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "stat": bench_stat, "knn": bench_knn, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
+        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "stat": bench_stat, "knn": bench_knn, "cluster": bench_cluster, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)
