@@ -18,6 +18,8 @@ from . import _gmm
 _NOT_ON_DEVICE = ("{} is not implemented: the reference delegates it to scikit-learn's sequential coordinate-descent / "
                   "fixed-point solvers seeded from scikit-learn's own random stream, which has no device counterpart "
                   "here.  Available: gmm ('diag', 'spherical'), pca and what builds on them.")
+_NMF_ELSEWHERE = ("{} still raises here; the working code is {}: NMF by coordinate descent runs on the device "
+                  "(csrc/nmf.hip).")
 
 
 def _pyplot():
@@ -246,13 +248,14 @@ class imlocal:
         raise NotImplementedError(_NOT_ON_DEVICE.format("imlocal.ica (FastICA)"))
 
     def nmf(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_ON_DEVICE.format("imlocal.nmf (NMF)"))
+        raise NotImplementedError(_NMF_ELSEWHERE.format("imlocal.nmf", "atomai_amd.stat.nmf.imlocal_nmf(stack, ...)"))
 
     def imblock_ica(self, *args, **kwargs):
         raise NotImplementedError(_NOT_ON_DEVICE.format("imlocal.imblock_ica (FastICA)"))
 
     def imblock_nmf(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_ON_DEVICE.format("imlocal.imblock_nmf (NMF)"))
+        raise NotImplementedError(_NMF_ELSEWHERE.format("imlocal.imblock_nmf",
+                                                        "atomai_amd.stat.nmf.imblock_nmf(stack, ...)"))
 
     # ------------------------------------------------------------------------------------------------ plots
     @classmethod
@@ -408,9 +411,11 @@ def update_classes(coordinates: Union[Dict[int, np.ndarray], np.ndarray], nn_inp
 
 class SlidingFFTNMF:
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_ON_DEVICE.format("SlidingFFTNMF"))
+        raise NotImplementedError(_NMF_ELSEWHERE.format("atomai_amd.stat.SlidingFFTNMF",
+                                                        "atomai_amd.stat.fft_nmf.SlidingFFTNMF"))
 
 
 class SpectralUnmixer:
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_ON_DEVICE.format("SpectralUnmixer"))
+        raise NotImplementedError(_NMF_ELSEWHERE.format("atomai_amd.stat.SpectralUnmixer",
+                                                        "atomai_amd.stat.unmixer.SpectralUnmixer (method='nmf')"))

@@ -1,0 +1,85 @@
+"""Spectral unmixing of hyperspectral cubes (atomai/stat/unmixer.py): the NMF method, on the device (csrc/nmf.hip)."""
+import warnings
+
+import numpy as np
+
+from . import _nmf
+
+_NMF_KWARGS = ("init", "max_iter", "tol", "random_state")
+
+
+class SpectralUnmixer:
+    """Decomposes an (h, w, e) hyperspectral cube into ``n_components`` spectra and their abundance maps.
+
+    Args:
+        method: 'nmf'.  The reference's 'pca', 'ica' and 'gmm' raise NotImplementedError.
+        n_components: number of components (at most 32)
+        normalize: L1-normalise every spectrum before the decomposition; the abundances are scaled back
+        **kwargs: ``init``, ``max_iter`` (200), ``tol`` (1e-4), ``random_state`` of sklearn.decomposition.NMF
+    """
+
+    def __init__(self, method: str = 'nmf', n_components: int = 4, normalize: bool = False, **kwargs):
+        if method in ("pca", "ica", "gmm"):
+            raise NotImplementedError(f"SpectralUnmixer(method='{method}') is not implemented: only method='nmf' runs "
+                                      "on the device (for PCA and GMM of image stacks see aoi.stat.imlocal)")
+        if method != "nmf":
+            raise ValueError("Method not recognized. Choose from 'nmf', 'pca', 'ica', 'gmm'.")
+        unknown = sorted(set(kwargs) - set(_NMF_KWARGS))
+        if unknown:
+            raise TypeError(f"unsupported NMF arguments {unknown}: the device solver takes {_NMF_KWARGS}")
+        self.method = method
+        self.n_components = n_components
+        self.normalize = normalize
+        self.kwargs = kwargs
+        self.components_ = None
+        self.abundance_maps_ = None
+        self.image_shape_ = None
+        self.n_iter_ = None
+
+    def fit(self, hspy_data: np.ndarray):
+        """Fits the model to the cube and returns (components (k, e), abundance maps (h, w, k))."""
+        hspy_data = np.asarray(hspy_data)
+        if hspy_data.ndim != 3:
+            raise ValueError("Input data must be a 3D hyperspectral cube (h, w, e).")
+        self.image_shape_ = hspy_data.shape[:2]
+        h, w, e = hspy_data.shape
+        spectra = hspy_data.reshape((h * w, e))
+        to_fit = spectra.copy()
+        if self.normalize:
+            l1_norms = np.sum(spectra, axis=1, keepdims=True)
+            l1_norms[l1_norms == 0] = 1
+            to_fit = spectra / l1_norms
+        min_val = np.min(to_fit)
+        if min_val < 0:
+            warnings.warn(f"NMF requires non-negative data. Shifting data by {-min_val:.2f}.")
+            to_fit = to_fit - min_val
+        res = _nmf.fit_nmf(to_fit, self.n_components, **self.kwargs)
+        self.n_iter_ = res["n_iter"]
+        self.components_ = res["H"].cpu().numpy()
+        abundances = res["W"].cpu().numpy()
+        if self.normalize:
+            abundances = abundances * l1_norms
+        self.abundance_maps_ = abundances.reshape((h, w, self.n_components))
+        return self.components_, self.abundance_maps_
+
+    def plot_results(self, x_axis_vals=None, x_axis_units=None, **kwargs):
+        if self.components_ is None:
+            print("You must run .fit() first.")
+            return
+        from .multivar import _pyplot
+        plt = _pyplot()
+        n_cols = self.n_components
+        fig, axes = plt.subplots(2, n_cols, figsize=kwargs.get("figsize", (n_cols * 3.5, 6)), squeeze=False)
+        xaxis = x_axis_vals if x_axis_vals is not None else np.arange(0, self.components_.shape[-1])
+        for i in range(n_cols):
+            axes[0, i].plot(xaxis, self.components_[i, :])
+            axes[0, i].set_title(f'{self.method.upper()} Component {i + 1}')
+            axes[0, i].set_xlabel(x_axis_units if x_axis_units is not None else 'Energy Bin')
+            if i == 0:
+                axes[0, i].set_ylabel('Intensity')
+            im = axes[1, i].imshow(self.abundance_maps_[..., i], cmap=kwargs.get("cmap", "seismic"))
+            axes[1, i].set_title(f'Abundance Map {i + 1}')
+            axes[1, i].axis('off')
+            fig.colorbar(im, ax=axes[1, i], fraction=0.046, pad=0.04)
+        plt.tight_layout()
+        plt.show()

@@ -737,6 +737,41 @@ int amx_cluster_label(const double* spts, long N, const int* ssid, const long* s
 int amx_cluster_stats(const double* pts, long N, const long* members, long M, const long* moff, long K, long* count,
                       double* mean, double* var, void* stream);
 
+/* ---- non-negative matrix factorisation by coordinate descent (sklearn.decomposition.NMF(solver='cd') behind
+ * imlocal.nmf, SlidingFFTNMF and SpectralUnmixer), csrc/nmf.hip.  X [n][d] row-major, float32 (is_f64 == 0) or float64,
+ * n, d < 2^31, 1 <= k <= 32; every product, sum and update is fp64; no atomics: two runs give the same bits.
+ * One half-step updates T [R][k] with F [L][k] fixed: trans == 0: T = W, F = H^T, R = n, L = d;  trans != 0: T = H^T,
+ * F = W, R = d, L = n (X is read transposed; both layouts load it coalesced).
+ * amx_nmf_splits: S, the number of chunks the reduction axis is split into: a function of (n, d, k, trans) only.
+ * amx_nmf_xf: P [S][R][k] fp64, P[s][r][t] = sum over j in chunk s of X(r, j) F[j][t], each in a fixed order.
+ * amx_nmf_cd: one thread per row i of T: XF[i] = sum_s P[s][i] in split order, then for t = 0 .. k-1:
+ *   grad = -XF[i][t] + sum_r FF[t][r] T[i][r] (r ascending); violation += |T[i][t] == 0 ? min(0, grad) : grad|;
+ *   if FF[t][t] != 0: T[i][t] = max(T[i][t] - grad / FF[t][t], 0).  FF [k][k] = F^T F.  Workgroup g owns the rows
+ *   [g A, (g + 1) A), A = amx_nmf_rows(), and writes Pv [G] (its violation) and Pg [G][k][k] (T^T T of its rows AFTER the
+ *   update), G = ceil(R / A).  gram_only != 0: no update (P, FF may be NULL), Pv = 0, Pg from T as it is.
+ * amx_nmf_reduce: adds the partials in workgroup order: *viol (optional) and gram [k][k]. */
+long amx_nmf_rows(void);
+long amx_nmf_splits(long n, long d, int k, int trans);
+int amx_nmf_xf(const void* X, int is_f64, long n, long d, int trans, const double* F, int k, double* P, void* stream);
+int amx_nmf_cd(const double* P, long S, long R, int k, const double* FF, double* T, int gram_only, double* Pv, double* Pg,
+               void* stream);
+int amx_nmf_reduce(const double* Pv, const double* Pg, long G, int k, double* viol, double* gram, void* stream);
+
+/* ---- sliding-window FFT features (SlidingFFTNMF.process_fft: Hamming table, fft2, fftshift, abs, log1p, centre crop,
+ * ndimage.zoom(order=1)), csrc/fftwin.hip.  One workgroup per window, nw0 x nw1 windows of wx x wy <= 128 x 128 pixels;
+ * pixel (x, y) of window (a, b) is img[base + (a step0 + x) stride0 + (b step1 + y) stride1], img holds len fp64 values
+ * (the call is refused if a window would leave it).  ham [wx][wy] or NULL.  cx, sx [wx], cy, sy [wy]: cos and sin of
+ * 2 pi m / N.  Cropped shifted indices [x_min, x_min + ncx) x [y_min, y_min + ncy); shifted index s is frequency
+ * (s - N/2) mod N.  Zoom tables per output row (zx0, zx1 int32 rows of the crop, zxa, zxb fp64 weights, [nox]) and
+ * column ([noy]): out = sum of mag[i][j] * wx * wy over (i, j) in {zx0, zx1} x {zy0, zy1}, axis 0 outer; an entry with a
+ * negative index gives 0.  out [nw0 nw1][nox noy] fp64; flags [nw0 nw1] int32: bit 0 = some output of the window is
+ * non-zero, bit 1 = some output is not finite. */
+int amx_fftwin(const double* img, long len, long base, long stride0, long stride1, long step0, long step1, long nw0,
+               long nw1, int wx, int wy, const double* ham, const double* cx, const double* sx, const double* cy,
+               const double* sy, int x_min, int ncx, int y_min, int ncy, const int* zx0, const int* zx1, const double* zxa,
+               const double* zxb, int nox, const int* zy0, const int* zy1, const double* zya, const double* zyb, int noy,
+               double* out, int* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) — one JSON line each, written to gpurun_out/.
-   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec|denoiser|stat|knn [--unfused-head]
+   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec|denoiser|stat|knn|cluster|nmf [--unfused-head]
 """
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -1178,6 +1178,104 @@ def bench_cluster(members=12, frames=64, per_frame=4000, sigma=0.15, eps=0.5, mi
     return res
 
 
+def bench_nmf(hw=512, k=4, iters=1000, reps=20, emit=True):
+    """NMF on the device at the reference's own SlidingFFTNMF setting: a ``hw`` x ``hw`` image gives 841 windows of 64 x 64
+    and 4096 features each.  ``fit_nmf`` for ``iters`` iterations (tol = 0, init='random') against scikit-learn on the
+    host where it imports, the two half-steps' product kernels alone (device events; achieved bytes/s of X), the FFT
+    front end alone, and ``analyze_image`` end to end."""
+    import tempfile
+    from atomai_amd.stat import _nmf
+    from atomai_amd.stat.fft_nmf import SlidingFFTNMF
+    rng = np.random.default_rng(0)
+    yy, xx = np.mgrid[:hw, :hw]
+    img = (np.where(xx < hw // 2, np.sin(2 * np.pi * xx / 6.0) * np.sin(2 * np.pi * yy / 6.0), np.sin(2 * np.pi * (xx + yy) / 9.0))
+           + np.where(yy < hw // 3, np.sin(2 * np.pi * yy / 4.0), 0.0) + 0.2 * rng.normal(size=(hw, hw)))
+
+    def wall(fn, n):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return ts, out
+    s = SlidingFFTNMF(components=k)
+    norm = s._normalised(img)
+    s._features(norm, s.windows_shape)                                   # warm-up: library load, allocator
+    t_fft, X = wall(lambda: s._features(norm, s.windows_shape), reps)
+    n, d = X.shape
+    _nmf.fit_nmf(X, k, init="random", random_state=42, tol=0, max_iter=3)
+    t_fit, res = wall(lambda: _nmf.fit_nmf(X, k, init="random", random_state=42, tol=0, max_iter=iters), 3)
+    t_fit = float(np.median(t_fit))
+    X32 = X.to(torch.float32)
+    halves = {}
+    for tag, Xd in (("float64", X), ("float32", X32)):
+        W, Ht = res["W"].clone(), res["H"].T.contiguous()
+        hw_, hh = _nmf._Half(Xd, k, 0, W), _nmf._Half(Xd, k, 1, Ht)
+        for name, half, F in (("W", hw_, Ht), ("Ht", hh, W)):
+            ev = []
+            for _ in range(reps + 3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                L.call("amx_nmf_xf", L.ptr(Xd), int(Xd.dtype == torch.float64), n, d, half.trans, L.ptr(F), k, L.ptr(half.P),
+                       L.stream_ptr(Xd))
+                e1.record()
+                ev.append((e0, e1))
+            torch.cuda.synchronize()
+            ms = float(np.median([a.elapsed_time(b) for a, b in ev[3:]]))
+            halves[f"{tag}_{name}"] = {"ms": round(ms, 4), "splits": half.S,
+                                       "GBps_of_X": round(n * d * Xd.element_size() / ms / 1e6, 1)}
+    with tempfile.TemporaryDirectory() as tmp:
+        t_all, (comp, ab) = wall(lambda: SlidingFFTNMF(components=k).analyze_image(img, os.path.join(tmp, "b")), 3)
+    t_all = float(np.median(t_all))
+    fft_ms = float(np.median(t_fft)) * 1e3
+    res_d = {"metric": f"fit_nmf, {n} x {d} float64, k = {k}, init='random', {iters} iterations (tol = 0)",
+             "value": round(t_fit, 4), "unit": "s", "n_gpus": 1, "dtype": "fp64", "ms_per_iteration": round(t_fit / iters * 1e3, 4),
+             "xf_kernels": halves, "ms_fft_front_end": round(fft_ms, 3), "s_analyze_image": round(t_all, 4),
+             "analyze_image_shapes": [list(comp.shape), list(ab.shape)]}
+    log = [f"# python tools/bench_extra.py nmf - {hw} x {hw} image, windows {s.window_size_x} x {s.window_size_y}, step "
+           f"{s.window_step_x}: {n} windows x {d} features, k = {k}",
+           f"fit_nmf, float64 X, init='random', {iters} iterations (tol = 0), one read-back per iteration   {t_fit:9.4f} s "
+           f"(median of 3, wall clock; {t_fit / iters * 1e3:.4f} ms per iteration = 2 half-steps)"]
+    for key, v in halves.items():
+        log.append(f"amx_nmf_xf alone, {key:<11s} ({v['splits']:2d} splits)   {v['ms']:8.4f} ms (median of {reps}, device events) = "
+                   f"{v['GBps_of_X']:8.1f} GB/s of X")
+    log += [f"amx_fftwin, {n} windows read in place from the image                                   {fft_ms:9.3f} ms "
+            f"(median of {reps}, wall clock, tables and read-back of the flag included)",
+            f"SlidingFFTNMF.analyze_image end to end (to convergence at tol = 1e-4, .npy files written)      {t_all:9.4f} s "
+            f"(median of 3)"]
+    try:
+        from sklearn.decomposition import NMF
+    except ImportError:
+        NMF = None
+    if NMF is None:
+        res_d["cpu_baseline"] = None
+        log.append("scikit-learn does not import here: NMF on the host was NOT measured")
+    else:
+        import warnings
+        Xh = X.cpu().numpy()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            t0 = time.perf_counter()
+            m = NMF(k, init="random", random_state=42, tol=0, max_iter=iters, solver="cd")
+            Wh = m.fit_transform(Xh)
+            t_ref = time.perf_counter() - t0
+        err = max(float(np.abs(res["W"].cpu().numpy() - Wh).max() / np.abs(Wh).max()),
+                  float(np.abs(res["H"].cpu().numpy() - m.components_).max() / np.abs(m.components_).max()))
+        res_d["cpu_baseline"] = {"s_sklearn": round(t_ref, 4), "n_iter": int(m.n_iter_), "max_rel_difference": err}
+        log.append(f"host, same matrix, same run: sklearn NMF(solver='cd'), {m.n_iter_} iterations                       "
+                   f"{t_ref:9.4f} s (max difference over max value of W, H: {err:.1e})")
+    res_d["log"] = log
+    if emit:
+        print("\n".join(log))
+        print(json.dumps(res_d), flush=True)
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        with open(os.path.join(root, "profiles", "nmf_bench.log"), "w") as f:
+            f.write("\n".join(log) + "\n")
+    return res_d
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["rvae", "predict"]
     unfused_head = "--unfused-head" in what            # denoiser: time the three-launch tail instead of the fused head
@@ -1188,6 +1286,6 @@ if __name__ == "__main__":
         if w == "denoiser":
             res[w] = bench_denoiser(fused_head=not unfused_head)
             continue
-        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "stat": bench_stat, "knn": bench_knn, "cluster": bench_cluster, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
+        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "stat": bench_stat, "knn": bench_knn, "cluster": bench_cluster, "nmf": bench_nmf, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)
