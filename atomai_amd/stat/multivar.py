@@ -15,9 +15,8 @@ from ..nets._linear import _gemm
 from ..utils import extract_subimages
 from . import _gmm
 
-_NOT_ON_DEVICE = ("{} is not implemented: the reference delegates it to scikit-learn's sequential coordinate-descent / "
-                  "fixed-point solvers seeded from scikit-learn's own random stream, which has no device counterpart "
-                  "here.  Available: gmm ('diag', 'spherical'), pca and what builds on them.")
+_ICA_ELSEWHERE = ("{} still raises here; the working code is {}: FastICA (parallel, fixed point) runs on the device "
+                  "(csrc/ica.hip).")
 _NMF_ELSEWHERE = ("{} still raises here; the working code is {}: NMF by coordinate descent runs on the device "
                   "(csrc/nmf.hip).")
 
@@ -245,13 +244,14 @@ class imlocal:
 
     # ------------------------------------------------------------------------------------------------ not offered
     def ica(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_ON_DEVICE.format("imlocal.ica (FastICA)"))
+        raise NotImplementedError(_ICA_ELSEWHERE.format("imlocal.ica", "atomai_amd.stat.ica.imlocal_ica(stack, ...)"))
 
     def nmf(self, *args, **kwargs):
         raise NotImplementedError(_NMF_ELSEWHERE.format("imlocal.nmf", "atomai_amd.stat.nmf.imlocal_nmf(stack, ...)"))
 
     def imblock_ica(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_ON_DEVICE.format("imlocal.imblock_ica (FastICA)"))
+        raise NotImplementedError(_ICA_ELSEWHERE.format("imlocal.imblock_ica",
+                                                        "atomai_amd.stat.ica.imblock_ica(stack, ...)"))
 
     def imblock_nmf(self, *args, **kwargs):
         raise NotImplementedError(_NMF_ELSEWHERE.format("imlocal.imblock_nmf",

@@ -12,16 +12,22 @@ class SpectralUnmixer:
     """Decomposes an (h, w, e) hyperspectral cube into ``n_components`` spectra and their abundance maps.
 
     Args:
-        method: 'nmf'.  The reference's 'pca', 'ica' and 'gmm' raise NotImplementedError.
+        method: 'nmf'.  The reference's 'pca', 'ica' and 'gmm' raise NotImplementedError ('ica' runs as
+            ``atomai_amd.stat.ica.ICAUnmixer``).
         n_components: number of components (at most 32)
         normalize: L1-normalise every spectrum before the decomposition; the abundances are scaled back
         **kwargs: ``init``, ``max_iter`` (200), ``tol`` (1e-4), ``random_state`` of sklearn.decomposition.NMF
     """
 
     def __init__(self, method: str = 'nmf', n_components: int = 4, normalize: bool = False, **kwargs):
-        if method in ("pca", "ica", "gmm"):
+        if method == "ica":
+            raise NotImplementedError("SpectralUnmixer(method='ica') still raises here (this class runs method='nmf' "
+                                      "only); the working code is atomai_amd.stat.ica.ICAUnmixer: FastICA runs on the "
+                                      "device (csrc/ica.hip)")
+        if method in ("pca", "gmm"):
             raise NotImplementedError(f"SpectralUnmixer(method='{method}') is not implemented: only method='nmf' runs "
-                                      "on the device (for PCA and GMM of image stacks see aoi.stat.imlocal)")
+                                      "on the device (for ICA see atomai_amd.stat.ica.ICAUnmixer, for PCA and GMM of "
+                                      "image stacks aoi.stat.imlocal)")
         if method != "nmf":
             raise ValueError("Method not recognized. Choose from 'nmf', 'pca', 'ica', 'gmm'.")
         unknown = sorted(set(kwargs) - set(_NMF_KWARGS))

@@ -772,6 +772,26 @@ int amx_fftwin(const double* img, long len, long base, long stride0, long stride
                const double* zxb, int nox, const int* zy0, const int* zy1, const double* zya, const double* zyb, int noy,
                double* out, int* flags, void* stream);
 
+/* ---- FastICA passes (sklearn.decomposition.FastICA, algorithm='parallel', behind imlocal.ica and
+ * SpectralUnmixer('ica')), csrc/ica.hip.  n, d < 2^31, 1 <= k <= 32; everything is fp64; no atomics: two runs give the same
+ * bits.  The whitening's Gram matrix and the k x k symmetric decorrelation are the caller's (BLAS and eigh through torch).
+ * amx_ica_project: out [k][n] fp64, out[t][r] = scale * sum_j M[t][j] (X[r][j] - mean[j]); X [n][d] row-major, float32
+ *   (is_f64 == 0) or float64, read in place; mean [d], M [k][d].
+ * amx_ica_blocks: G, the number of workgroups of amx_ica_step: a function of n only (0 for a bad n or k).
+ * amx_ica_step: one fixed-point step over X1 [k][n], read once: Y = W X1 (W [k][k]), g = G(Y), and per workgroup b
+ *   Pg [G][k][k] = its samples' part of g X1^T, Ph [G][k] = its samples' part of sum_n G'(Y).  fun 0: G = tanh(alpha y),
+ *   G' = alpha (1 - G^2), 1 <= alpha <= 2;  1: G = y exp(-y^2 / 2), G' = (1 - y^2) exp(-y^2 / 2);  2: G = y^3, G' = 3 y^2.
+ * amx_ica_reduce: A [k][k] = (sum_b Pg[b]) / n - diag((sum_b Ph[b]) / n) W, the sums in a fixed order; G must be
+ *   amx_ica_blocks(n, k).
+ * amx_ica_rowstd: sd [k], sd[i] = sqrt(mean_j (S[i][j] - mean_j S[i][j])^2) of S [k][n] (numpy.std), in a fixed order. */
+long amx_ica_blocks(long n, int k);
+int amx_ica_project(const void* X, int is_f64, long n, long d, const double* mean, const double* M, int k, double scale,
+                    double* out, void* stream);
+int amx_ica_step(const double* X1, long n, int k, int fun, double alpha, const double* W, double* Pg, double* Ph,
+                 void* stream);
+int amx_ica_reduce(const double* Pg, const double* Ph, long G, int k, long n, const double* W, double* A, void* stream);
+int amx_ica_rowstd(const double* S, int k, long n, double* sd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

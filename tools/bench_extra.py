@@ -1,5 +1,5 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) — one JSON line each, written to gpurun_out/.
-   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec|denoiser|stat|knn|cluster|nmf [--unfused-head]
+   python tools/bench_extra.py rvae|jrvae|predict|dkl|losses|imspec|denoiser|stat|knn|cluster|nmf|ica [--unfused-head]
 """
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -886,12 +886,9 @@ def bench_refine(frames=4, hw=1024, spacing=16, d=4, sigma=1.6, cycles=300, samp
     return res
 
 
-def bench_stat(frames=20, per_frame=1000, r=32, C=3, classes=10, noise=0.05, n_pca=4, em_iters=20, emit=True):
-    """stat.imlocal on a synthetic stack of frames * per_frame windows of r x r x C (D = r r C) cut from frames that carry
-    `classes` planted prototypes + noise: gmm(n_components=classes) and pca(n_pca) end to end, the EM pass kernel alone
-    (event-timed; GB/s against the N D 4 bytes of the stack, which one pass must read at least once), and — if
-    scikit-learn imports here — the reference-equivalent GaussianMixture(...).fit_predict on the same array in the same
-    run."""
+def _planted_stack(frames, per_frame, r, C, classes, noise):
+    """Frames that carry ``classes`` planted prototypes + noise at frames * per_frame window centres: (images,
+    coordinates per frame, planted class of every window)."""
     rs = np.random.default_rng(0)
     side = int(np.ceil(np.sqrt(per_frame)))
     H = (side + 2) * r
@@ -909,6 +906,16 @@ def bench_stat(frames=20, per_frame=1000, r=32, C=3, classes=10, noise=0.05, n_p
             planted.append(k)
         coords[b] = np.array(rows, dtype=np.float64)
     planted = np.array(planted)
+    return imgs, coords, planted
+
+
+def bench_stat(frames=20, per_frame=1000, r=32, C=3, classes=10, noise=0.05, n_pca=4, em_iters=20, emit=True):
+    """stat.imlocal on a synthetic stack of frames * per_frame windows of r x r x C (D = r r C) cut from frames that carry
+    `classes` planted prototypes + noise: gmm(n_components=classes) and pca(n_pca) end to end, the EM pass kernel alone
+    (event-timed; GB/s against the N D 4 bytes of the stack, which one pass must read at least once), and — if
+    scikit-learn imports here — the reference-equivalent GaussianMixture(...).fit_predict on the same array in the same
+    run."""
+    imgs, coords, planted = _planted_stack(frames, per_frame, r, C, classes, noise)
     dev = "cuda" if torch.cuda.is_available() else "cpu"
     from atomai_amd.stat import _gmm
     import warnings
@@ -1276,6 +1283,127 @@ def bench_nmf(hw=512, k=4, iters=1000, reps=20, emit=True):
     return res_d
 
 
+def bench_ica(frames=20, per_frame=1000, r=32, C=3, classes=10, noise=0.05, k=10, reps=20, emit=True):
+    """FastICA on the device at the stat benchmark's own stack (frames * per_frame windows of r x r x C, planted classes),
+    k components, random_state = 1: ``fit_ica`` end to end (wall clock around a synchronise), its split into Gram + eigh,
+    projection and iterations (device events), the step + reduce pair alone (device events; bytes of X1 per second), the
+    same iteration written as torch fp64 operations on the device, interleaved with the fused pair and with a second
+    series of the fused pair (the A/A spread), and -- where scikit-learn imports -- FastICA on the host on the same matrix."""
+    import warnings
+    from atomai_amd.stat import _ica
+    from atomai_amd.stat.nmf import _stack_matrix
+    imgs, coords, _ = _planted_stack(frames, per_frame, r, C, classes, noise)
+    X = torch.from_numpy(_stack_matrix(aoi.stat.imlocal(imgs, coords, r, 0))).cuda()
+    n, d = X.shape
+
+    def events(fn, n_rep):
+        """Median and the individual times (ms) of ``n_rep`` runs of fn between device events, 3 warm-up runs dropped."""
+        ev = []
+        for _ in range(n_rep + 3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            ev.append((e0, e1))
+        torch.cuda.synchronize()
+        ms = [a.elapsed_time(b) for a, b in ev[3:]]
+        return float(np.median(ms)), ms
+
+    def fit():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return _ica.fit_ica(X, k, random_state=1)
+    fit()                                                                # warm-up: library load, allocator, BLAS, eigh
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fit()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    t_fit = float(np.median(ts))
+    ms_white, _ = events(lambda: _ica._whitening(X, k), reps)
+    mean, K, u, sigma = _ica._whitening(X, k)
+    ms_proj, _ = events(lambda: _ica.project(X, mean, K, np.sqrt(n)), reps)
+    X1 = _ica.project(X, mean, K, np.sqrt(n))
+    W = _ica.sym_decorrelation(torch.from_numpy(np.random.RandomState(1).normal(size=(k, k))).cuda())
+    step = _ica._Step(X1, 0, 1.0)
+
+    def fused_iteration():
+        W1 = _ica.sym_decorrelation(step.run(W))
+        return ((W1 * W).sum(1).abs() - 1.0).abs().max()
+
+    def torch_step():
+        g = torch.tanh(W @ X1)
+        return g @ X1.T / n - (1.0 - g * g).mean(1)[:, None] * W
+
+    def torch_iteration():
+        W1 = _ica.sym_decorrelation(torch_step())
+        return ((W1 * W).sum(1).abs() - 1.0).abs().max()
+    ms_iter, _ = events(lambda: float(fused_iteration()), reps)           # with the read-back of lim, as in the fit
+    ms_iter_torch, _ = events(lambda: float(torch_iteration()), reps)
+    ab = {"fused_a": [], "torch": [], "fused_b": []}                     # interleaved: fused, torch, fused, ...
+    for rep in range(reps + 3):
+        for tag, fn in (("fused_a", lambda: step.run(W)), ("torch", torch_step), ("fused_b", lambda: step.run(W))):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            ab[tag].append((e0, e1))
+    torch.cuda.synchronize()
+    ab = {tag: float(np.median([a.elapsed_time(b) for a, b in ev[3:]])) * 1e3 for tag, ev in ab.items()}     # us
+    us_fused = 0.5 * (ab["fused_a"] + ab["fused_b"])
+    spread = abs(ab["fused_a"] - ab["fused_b"])
+    diff = float((step.run(W) - torch_step()).abs().max())
+    res_d = {"metric": f"fit_ica, {n} x {d} float32 stack, k = {k}, logcosh, random_state = 1, tol = 1e-4",
+             "value": round(t_fit, 4), "unit": "s", "n_gpus": 1, "dtype": "fp64", "n_iter": res["n_iter"],
+             "converged": res["converged"], "ms_gram_eigh": round(ms_white, 3), "ms_projection": round(ms_proj, 3),
+             "ms_one_iteration": round(ms_iter, 4), "ms_one_iteration_torch_step": round(ms_iter_torch, 4),
+             "us_step_reduce_fused": round(us_fused, 2),
+             "us_step_torch_ops": round(ab["torch"], 2), "us_fused_a_a_spread": round(spread, 2),
+             "GBps_of_X1": round(k * n * 8 / us_fused / 1e3, 1), "blocks": step.G, "fused_vs_torch_max_abs": diff}
+    log = [f"# python tools/bench_extra.py ica - {n} windows x {d} features (float32 stack), k = {k}, logcosh, "
+           f"random_state = 1, one run",
+           f"fit_ica end to end, {res['n_iter']} iterations, converged {res['converged']}            {t_fit:9.4f} s "
+           f"(median of {reps}, wall clock around a synchronise)",
+           f"  Gram matrix over chunks + eigh + sign rule (whitening)                 {ms_white:9.3f} ms (median of {reps}, device events)",
+           f"  projection X1 = sqrt(n) K (X - mean)^T (amx_ica_project)               {ms_proj:9.3f} ms (median of {reps}, device events)",
+           f"  one iteration: step, reduce, decorrelation (eigh), lim read back       {ms_iter:9.4f} ms (median of {reps}, device events)",
+           f"  the same iteration with the step written as torch fp64 operations     {ms_iter_torch:9.4f} ms (median of {reps}, device events)",
+           f"step + reduce alone (amx_ica_step, amx_ica_reduce; {step.G} workgroups)       {us_fused:9.2f} us (median of {reps}, "
+           f"device events, mean of the two interleaved series) = {res_d['GBps_of_X1']} GB/s of X1",
+           f"the same step as torch fp64 operations, interleaved in the same run      {ab['torch']:9.2f} us; A/A spread of the "
+           f"fused pair {spread:.2f} us; results agree within {diff:.1e} (max abs)"]
+    try:
+        from sklearn.decomposition import FastICA
+    except ImportError:
+        FastICA = None
+    if FastICA is None:
+        res_d["cpu_baseline"] = None
+        log.append("scikit-learn does not import here: FastICA on the host was NOT measured")
+    else:
+        Xh = X.cpu().numpy().astype(np.float64)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            t0 = time.perf_counter()
+            m = FastICA(k, random_state=1)
+            Sh = m.fit_transform(Xh)
+            t_ref = time.perf_counter() - t0
+        err = max(float(np.abs(res["sources"].cpu().numpy() - Sh).max() / np.abs(Sh).max()),
+                  float(np.abs(res["components"].cpu().numpy() - m.components_).max() / np.abs(m.components_).max()))
+        res_d["cpu_baseline"] = {"s_sklearn": round(t_ref, 4), "n_iter": int(m.n_iter_), "max_rel_difference": err}
+        log.append(f"host, same matrix (as float64), same run: sklearn FastICA, {m.n_iter_} iterations      {t_ref:9.4f} s "
+                   f"(one run; max difference over max value of sources, components: {err:.1e})")
+    res_d["log"] = log
+    if emit:
+        print("\n".join(log))
+        print(json.dumps(res_d), flush=True)
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        with open(os.path.join(root, "profiles", "ica_bench.log"), "w") as f:
+            f.write("\n".join(log) + "\n")
+    return res_d
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["rvae", "predict"]
     unfused_head = "--unfused-head" in what            # denoiser: time the three-launch tail instead of the fused head
@@ -1286,6 +1414,6 @@ if __name__ == "__main__":
         if w == "denoiser":
             res[w] = bench_denoiser(fused_head=not unfused_head)
             continue
-        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "stat": bench_stat, "knn": bench_knn, "cluster": bench_cluster, "nmf": bench_nmf, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
+        res[w] = {"rvae": bench_rvae, "jrvae": bench_jrvae, "predict": bench_predict, "dkl": bench_dkl, "dklfit": bench_dkl_fit, "locate": bench_locate, "refine": bench_refine, "stat": bench_stat, "knn": bench_knn, "cluster": bench_cluster, "nmf": bench_nmf, "ica": bench_ica, "segfamily": bench_segfamily, "losses": bench_losses, "imspec": bench_imspec,
                   "predict4096": bench_predict_full}[w]()
     json.dump(res, open("gpurun_out/bench_extra.json", "w"), indent=1)
