@@ -388,13 +388,21 @@ def _as_frames(images: np.ndarray) -> np.ndarray:
 
 def update_classes(coordinates: Union[Dict[int, np.ndarray], np.ndarray], nn_input: np.ndarray,
                    method: str = 'threshold', **kwargs: float) -> Dict[int, np.ndarray]:
-    """New classes for the located atoms from a GMM of the image patches around them: ``method='gmm_local'`` with
+    """New classes for the located atoms.  ``method='gmm_local'``: from a GMM of the image patches around them, with
     ``n_components``, ``window_size`` and optionally ``coord_class`` (default 0: only atoms of that class are kept and
-    re-classified, 0-based; atoms whose window leaves the image are dropped).  ``coordinates``: the Locator's dictionary,
-    or one frame's table together with that frame as ``nn_input``.  Returns a new dictionary.  The intensity-based
-    methods of the reference ('threshold', 'kmeans', 'meanshift') are not implemented."""
+    re-classified, 0-based; atoms whose window leaves the image are dropped).  ``method='threshold'`` (``thresh``,
+    the reference's default) and ``method='meanshift'`` (``quantile``): from the mean intensity in the window of side
+    ``window_size`` (default 3) around every atom, through ``stat.intensity.update_classes`` (csrc/intensity.hip).
+    ``coordinates``: the Locator's dictionary, or one frame's table together with that frame as ``nn_input``.  Returns a
+    new dictionary.  ``method='kmeans'`` still raises here; it runs as
+    ``atomai_amd.stat.intensity.update_classes(..., method='kmeans')``."""
+    if method == "kmeans":
+        raise NotImplementedError("update_classes(method='kmeans') still raises here; the working code is "
+                                  "atomai_amd.stat.intensity.update_classes(..., method='kmeans'): k-means of the "
+                                  "intensities runs on the device (csrc/intensity.hip).")
     if method != "gmm_local":
-        raise NotImplementedError(f"update_classes(method='{method}') is not implemented; use method='gmm_local'")
+        from . import intensity
+        return intensity.update_classes(coordinates, nn_input, method, **kwargs)
     n_components, window_size = kwargs.get("n_components"), kwargs.get("window_size")
     if n_components is None or window_size is None:
         raise AttributeError("method='gmm_local' needs n_components and window_size")

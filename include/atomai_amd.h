@@ -792,6 +792,34 @@ int amx_ica_step(const double* X1, long n, int k, int fun, double alpha, const d
 int amx_ica_reduce(const double* Pg, const double* Ph, long G, int k, long n, const double* W, double* A, void* stream);
 int amx_ica_rowstd(const double* S, int k, long n, double* sd, void* stream);
 
+/* ---- one-dimensional clustering of atom intensities (atomai/stat/multivar.py: update_classes = sklearn.cluster
+ * estimate_bandwidth, MeanShift(bin_seeding=True) and KMeans on one column), csrc/intensity.hip.  Everything is fp64,
+ * 1 <= n < 2^31; xs [n] is the column sorted ascending (the caller sorts).  No floating-point atomics; every sum over
+ * rows [lo, hi) is formed as: thread t of 256 adds rows lo + t, lo + t + 256, ... in order, then the 256 partials are
+ * added by halving (p[t] += p[t + w], w = 128, 64, ... 1): two runs give the same bits.
+ * amx_kth_gap_1d: 1 <= K <= n.  gap [n], gap[i] = distance from xs[i] to its K-th nearest value of xs, itself counted at
+ *   distance 0 (the last column of NearestNeighbors(n_neighbors=K).kneighbors) = min over l in [max(0, i-K+1),
+ *   min(i, n-K)] of max(xs[i] - xs[l], xs[l+K-1] - xs[i]).  partial [G], G = amx_kth_gap_blocks(n) = ceil(n / 256): the sum
+ *   of the gaps of rows [256 g, 256 g + 256); *mean_out = (sum of partial, as a range sum) / n.
+ * amx_meanshift_1d: one workgroup per seed, S seeds, bw > 0, max_iter >= 0; _mean_shift_single_seed of scikit-learn:
+ *   m = seed, it = 0; repeat: members = rows with fabs(x - m) <= bw (a contiguous range, both ends found by binary search
+ *   on that test); none: stop with count 0; old = m, m = (range sum) / count; stop if fabs(m - old) <= 1e-3 bw or
+ *   it == max_iter; ++it.  centre [S] = m, count [S] int64 = members of the last range, iters [S] int64 = it.
+ * amx_lloyd_1d: 1 <= k <= 32, tol >= 0, one workgroup.  Round: centres sorted by (value, index); the rows > the midpoint
+ *   (a + b) * 0.5 of two neighbouring centres belong to the upper one, a row equal to it to the one with the smaller
+ *   index; centre = (range sum) / count, an EMPTY range keeps its centre (scikit-learn relocates it).  Stops after the
+ *   round in which no range differs from the round before, or the sum of squared centre shifts is <= tol, or after
+ *   max_iter rounds.  centres_out [k] in the order of centres_in; *n_iter int64 = rounds run.
+ * amx_assign_1d: x [n] UNSORTED, n >= 0; label [n] int64 = the index c of the smallest fabs(x - centres[c]), the first of
+ *   equal ones; C >= 1 centres, any number (they pass through LDS 1024 at a time). */
+long amx_kth_gap_blocks(long n);
+int amx_kth_gap_1d(const double* xs, long n, long K, double* gap, double* partial, double* mean_out, void* stream);
+int amx_meanshift_1d(const double* xs, long n, const double* seeds, long S, double bw, long max_iter, double* centre,
+                     long* count, long* iters, void* stream);
+int amx_lloyd_1d(const double* xs, long n, const double* centres_in, int k, double tol, long max_iter,
+                 double* centres_out, long* n_iter, void* stream);
+int amx_assign_1d(const double* x, long n, const double* centres, long C, long* label, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
