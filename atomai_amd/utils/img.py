@@ -126,3 +126,178 @@ def get_coord_grid(imgdata: np.ndarray, step: int, return_dict: bool = True):
         coord = np.concatenate((coord, np.zeros((coord.shape[0], 1))), axis=-1)
         return {i: coord for i in range(imgdata.shape[0])}
     return np.concatenate([coord for _ in range(imgdata.shape[0])], axis=0)
+
+
+# ---- training patches and random sub-images (img.py:183-296, 353-389): the offsets are drawn on the host exactly as the
+# reference / scikit-learn draw them, the windows of ALL frames are gathered by one amx_crop_windows launch per array.
+def _windows(frames: np.ndarray, frame_idx, rows, cols, ph: int, pw: int):
+    """(windows (P, ph, pw, C) of frames.dtype, flag (P,)) of the (F, H, W, C) stack; flag as amx_crop_windows."""
+    from . import _lattice
+    win = np.stack((np.asarray(frame_idx), np.asarray(rows), np.asarray(cols)), axis=1).astype(np.int32)
+    return _lattice.crop_host(frames, win.reshape(-1, 3), ph, pw)
+
+
+def _patch_offsets(h: int, w: int, patch_size, num_patches, random_state):
+    """Top-left corners of scikit-learn's ``extract_patches_2d(max_patches=num_patches, random_state=...)``: random WITH
+    replacement, all rows drawn before all columns."""
+    import numbers
+    ph, pw = (patch_size, patch_size) if isinstance(patch_size, numbers.Integral) else patch_size
+    ph, pw = int(ph), int(pw)
+    if ph > h:
+        raise ValueError("Height of the patch should be less than the height of the image.")
+    if pw > w:
+        raise ValueError("Width of the patch should be less than the width of the image.")
+    if not isinstance(num_patches, numbers.Integral) or num_patches < 1:
+        raise ValueError(f"num_patches must be a positive integer, got {num_patches!r}")
+    every = (h - ph + 1) * (w - pw + 1)
+    m = min(int(num_patches), every)
+    rng = np.random.RandomState(random_state)
+    i = rng.randint(h - ph + 1, size=m)
+    j = rng.randint(w - pw + 1, size=m)
+    return ph, pw, i, j
+
+
+def _as_stack(a: np.ndarray) -> np.ndarray:
+    """(F, H, W) or (F, H, W, C) -> (F, H, W, C)."""
+    a = np.asarray(a)
+    if a.ndim not in (3, 4):
+        raise ValueError(f"expected a stack (n, h, w) or (n, h, w, c), got shape {a.shape}")
+    return a[..., None] if a.ndim == 3 else a
+
+
+def _drop_unit_channel(p: np.ndarray) -> np.ndarray:
+    return p[..., 0] if p.shape[-1] == 1 else p                # scikit-learn drops a colour axis of length 1
+
+
+def extract_patches(images: np.ndarray, masks: np.ndarray, patch_size: int, num_patches: int,
+                    **kwargs: int) -> Tuple[np.ndarray]:
+    """``num_patches`` random patches of every image-mask pair of two stacks (or of one 2-D pair), concatenated over the
+    frames (img.py:369-389).  The offsets follow scikit-learn's ``extract_patches_2d``: m = min(num_patches, number of
+    distinct patches) corners drawn WITH replacement from ``np.random.RandomState(random_state)`` (``**random_state``,
+    default 0), rows first, then columns; image and mask share them, and — the reference's behaviour — so does every
+    frame.  ``patch_size`` is an int or a (height, width) pair; a trailing channel axis of length 1 is dropped; the
+    dtypes are kept; a patch larger than the frame raises ``ValueError``.  scikit-learn is not imported."""
+    images, masks = np.asarray(images), np.asarray(masks)
+    images = images[None] if images.ndim == 2 else images
+    masks = masks[None] if masks.ndim == 2 else masks
+    n = min(len(images), len(masks))
+    images, masks = _as_stack(images[:n]), _as_stack(masks[:n])
+    if images.shape[1:3] != masks.shape[1:3]:
+        raise ValueError(f"images {images.shape[1:3]} and masks {masks.shape[1:3]} differ in size")
+    ph, pw, i, j = _patch_offsets(images.shape[1], images.shape[2], patch_size, num_patches, kwargs.get("random_state", 0))
+    frame_idx, rows, cols = np.repeat(np.arange(n), len(i)), np.tile(i, n), np.tile(j, n)
+    return tuple(_drop_unit_channel(_windows(a, frame_idx, rows, cols, ph, pw)[0]) for a in (images, masks))
+
+
+def extract_patches_(lattice_im: np.ndarray, lattice_mask: np.ndarray, patch_size: int, num_patches: int,
+                     **kwargs: int) -> Tuple[np.ndarray]:
+    """Patches of ONE image (h, w[, c]) and its mask at shared random offsets (img.py:353-366); see ``extract_patches``."""
+    lattice_im, lattice_mask = np.asarray(lattice_im), np.asarray(lattice_mask)
+    if lattice_im.ndim not in (2, 3) or lattice_mask.ndim not in (2, 3):
+        raise ValueError("extract_patches_ takes one image (h, w) or (h, w, c) and its mask")
+    return extract_patches(lattice_im[None], lattice_mask[None], patch_size, num_patches, **kwargs)
+
+
+def _centred(frames: np.ndarray, frame_idx, centres: np.ndarray, r: int):
+    """``get_imgstack`` for centres in several frames at once: windows [c - r//2, c - r//2 + r) around the centres
+    rounded half to even; (windows, keep) with keep False where the window leaves the frame or holds a NaN."""
+    lo = np.around(np.asarray(centres, dtype=np.float64)[:, :2]).astype(np.int64) - r // 2
+    lo = np.clip(lo, -2 ** 30, 2 ** 30)                        # (far-off centres stay outside, without int32 overflow)
+    stack, flag = _windows(frames, frame_idx, lo[:, 0], lo[:, 1], r, r)
+    return stack, flag == 0
+
+
+def _single(img: np.ndarray) -> np.ndarray:
+    img = np.asarray(img)
+    if img.ndim not in (2, 3):
+        raise ValueError(f"expected one image (h, w) or (h, w, c), got shape {img.shape}")
+    return img[None, ..., None] if img.ndim == 2 else img[None]
+
+
+def _kept(img: np.ndarray, com_xy: np.ndarray, window_size: int):
+    """What ``get_imgstack(img, com_xy, window_size)`` returns, with the gather on the device."""
+    if len(com_xy) == 0:
+        return None, None
+    stack, keep = _centred(_single(img), np.zeros(len(com_xy), dtype=np.int64), com_xy, int(window_size))
+    if not keep.any():
+        return None, None
+    stack = stack[keep]
+    return (stack[..., 0] if np.ndim(img) == 2 else stack), com_xy[keep]
+
+
+def _draw_pixels(h: int, w: int, window_size: int, num_images: int) -> np.ndarray:
+    """The reference's draws: scalar np.random.randint calls on numpy's GLOBAL state, row then column, repeats rejected."""
+    lo = window_size // 2 + 1
+    if num_images > max(h - 2 * lo, 0) * max(w - 2 * lo, 0):
+        raise ValueError("Number of images cannot be greater than the number of pixels they can be centred on")
+    seen, out = set(), []
+    while len(out) < num_images:
+        x = np.random.randint(lo, h - window_size // 2 - 1)
+        y = np.random.randint(lo, w - window_size // 2 - 1)
+        if (x, y) not in seen:
+            seen.add((x, y))
+            out.append((x, y))
+    return np.array(out, dtype=np.int64).reshape(-1, 2)
+
+
+def _draw_rows(n_rows: int, num_images: int) -> list:
+    if num_images > n_rows:
+        raise ValueError("Number of images cannot be greater than the available coordinates")
+    seen, out = set(), []
+    while len(out) < num_images:
+        i = np.random.randint(n_rows)
+        if i not in seen:
+            seen.add(i)
+            out.append(i)
+    return out
+
+
+def imcrop_randpx(img: np.ndarray, window_size: int, num_images: int, random_state: int = 0) -> Tuple[np.ndarray]:
+    """``num_images`` windows of side ``window_size`` centred on distinct random pixels of one image (img.py:183-211):
+    (windows, centres).  The draws come from numpy's global state (``np.random.seed`` reproduces the reference);
+    ``random_state`` is unused, as in the reference."""
+    h, w = np.shape(img)[:2]
+    return _kept(img, _draw_pixels(h, w, int(window_size), int(num_images)), window_size)
+
+
+def imcrop_randcoord(img: np.ndarray, coord: np.ndarray, window_size: int, num_images: int,
+                     random_state: int = 0) -> Tuple[np.ndarray]:
+    """``num_images`` windows centred on distinct random rows of ``coord`` (img.py:214-236): (windows, centres); a window
+    that leaves the image or holds a NaN is dropped.  Draws as for ``imcrop_randpx``."""
+    coord = np.asarray(coord)
+    com_xy = np.array([coord[i].tolist() for i in _draw_rows(len(coord), int(num_images))])
+    return _kept(img, com_xy, window_size)
+
+
+def extract_random_subimages(imgdata: np.ndarray, window_size: int, num_images: int,
+                             coordinates: Dict[int, np.ndarray] = None, **kwargs: int) -> Tuple[np.ndarray]:
+    """``num_images`` random sub-images of every frame of a stack (n, h, w[, c]), centred on atoms of one class
+    (``coordinates`` = the Locator's dictionary, ``**coord_class``, default 0; rows nearer than window_size // 2 + 1 to
+    an edge are removed first) or on random pixels (img.py:239-295).  Returns float64 (windows (n * num_images, ws, ws,
+    c), centres, frame numbers).  The draws are the reference's, frame by frame from numpy's global state; the windows of
+    all frames are gathered by one launch.  A window dropped for a NaN, which makes the reference's block assignment
+    fail, raises ``ValueError``; so does ``num_images`` above the available coordinates."""
+    from .coords import remove_edge_coord
+    imgdata = np.asarray(imgdata)
+    if imgdata.ndim < 4:
+        imgdata = imgdata[..., None]
+    window_size, num_images = int(window_size), int(num_images)
+    n, h, w = imgdata.shape[:3]
+    centres = []
+    for i in range(n):
+        if coordinates is None:
+            centres.append(_draw_pixels(h, w, window_size, num_images).astype(np.float64))
+        else:
+            coord = np.asarray(coordinates[i])
+            coord = coord[coord[:, -1] == kwargs.get("coord_class", 0)][:, :2]
+            coord = remove_edge_coord(coord, imgdata.shape[1:3], window_size // 2 + 1)
+            centres.append(np.array([coord[r].tolist() for r in _draw_rows(len(coord), num_images)],
+                                    dtype=np.float64).reshape(-1, 2))
+    com_all = np.concatenate(centres, axis=0) if centres else np.zeros((0, 2))
+    frames_all = np.repeat(np.arange(n), num_images).astype(np.float64)
+    stack, keep = _centred(imgdata, frames_all.astype(np.int64), com_all, window_size)
+    if not keep.all():
+        bad = int(np.argmin(keep))
+        raise ValueError(f"the window around {tuple(com_all[bad])} of frame {int(frames_all[bad])} holds a NaN or leaves "
+                         "the frame; the reference fails here as well (its block assignment needs every window)")
+    return stack.astype(np.float64), com_all, frames_all

@@ -820,6 +820,37 @@ int amx_lloyd_1d(const double* xs, long n, const double* centres_in, int k, doub
                  double* centres_out, long* n_iter, void* stream);
 int amx_assign_1d(const double* x, long n, const double* centres, long C, long* label, void* stream);
 
+/* ---- training sets for the Segmentor (atomai/utils/imgen.py: create_lattice_mask, create_multiclass_lattice_mask;
+ * atomai/utils/img.py: extract_patches, extract_random_subimages), csrc/lattice.hip.  All frames of a call are one flat
+ * atom table.  The only atomic is atomicMin on int32; no floating-point atomics; two runs give the same bits.
+ * Table: xy [N][2] fp64 = (row, column) coordinate; meta [N][3] int32 = (frame, channel, stamp id); 0 <= N < 2^31.
+ * Stamps: K squares; sside [K] int32 = the side m of each, odd and <= amx_lattice_max_side() (63); soff [K] int64 = the
+ *   first element of stamp k in stamps [S] fp64 (row-major m x m each; soff[k] + m*m <= S).
+ * Square of row i: x = rint(xy[i][0]), y = rint(xy[i][1]) (half to even), r1 = (m + 1) / 2, r2 = (m - 1) / 2; it covers
+ *   rows x-r1 .. x+r2-1 and columns y-r1 .. y+r2-1 (not centred; m = 5: x-3 .. x+1) and must lie inside [0, H) x [0, W).
+ * amx_lattice_owner: owner [F][H][W][C] int32, ZEROED by the caller, becomes min(0, -(i + 1) over the rows i whose square
+ *   covers the pixel in that frame and channel): the most negative key is the latest row.  *bad int32, set to INT_MAX by
+ *   the caller, becomes the smallest row that was REFUSED: non-finite coordinate; frame, channel or stamp id out of
+ *   range; even side or side above the maximum; a square that leaves the frame.  A refused row writes nothing else.
+ * amx_lattice_fill: out [F][H][W][CO] float (out_f64 = 0) or double, CO = C + background.  For key k = owner < 0, i = -k - 1:
+ *   v = stamps[soff[sid_i] + (p - (x_i - r1)) * m + (q - (y_i - r1))]; v = 0 for k = 0 (and for a key that names no row
+ *   covering the pixel).  background = 0: out[c] = v.  background = 1, nch [F] int32, n = nch[f] in [0, C]: for c < n,
+ *   out[c] = v; s = sum of those v added in the order c = 0, 1, ... in fp64; out[n] = 1 - s; out[c] = 0 for c > n; then
+ *   every out < 0 is replaced by 0 (class channels included, as the reference's clamp after the sum).  The library is
+ *   built with -ffp-contract=off.
+ * amx_crop_windows: a bit copy.  src [F][H][W][C] of esize = 4 or 8 bytes per element; win [P][3] int32 = (frame, first
+ *   row, first column); dst [P][ph][pw][C]; flag [P] int32 = -1 and NOTHING is written to dst if the frame is out of
+ *   range or the window is not wholly inside it; else 1 if is_float and the window holds a NaN (IEEE float / double by
+ *   esize), else 0.  One workgroup per window, the flag combined in LDS and stored once.  0 <= P < 2^31. */
+int amx_lattice_max_side(void);
+int amx_lattice_owner(const double* xy, const int* meta, long N, const int* sside, int K, int F, int H, int W, int C,
+                      int* owner, int* bad, void* stream);
+int amx_lattice_fill(const int* owner, const double* xy, const int* meta, long N, const int* sside, const long* soff, int K,
+                     const double* stamps, long S, const int* nch, int F, int H, int W, int C, int background, void* out,
+                     int out_f64, void* stream);
+int amx_crop_windows(const void* src, int esize, int is_float, int F, int H, int W, int C, const int* win, long P, int ph,
+                     int pw, void* dst, int* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,68 @@
+"""`not gpu` tier for the training-set functions (CPU SIMT emulator): csrc/lattice.hip against the numpy restatement and
+the golden of the reference's imgen.py / img.py and scikit-learn's extract_patches_2d."""
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
+import _lattice_checks as K  # noqa: E402
+
+
+@pytest.fixture(scope="module", autouse=True)
+def emulator():
+    if torch.cuda.is_available():
+        pytest.skip("emulator tier is for GPU-less hosts")
+    import emu_backend
+    emu_backend.use_emulator()
+
+
+def test_make_atom_against_reference():
+    K.check_make_atom()
+
+
+@pytest.mark.parametrize("name", K.mask_cases())
+def test_mask_against_reference(name):
+    K.check_mask_case(name)
+
+
+def test_class_column_is_not_modified():
+    K.check_input_unchanged()
+
+
+def test_owner_kernel_guards():
+    K.check_owner_kernel("cpu")
+
+
+def test_fill_float32_float64_and_background():
+    K.check_fill_dtypes("cpu")
+
+
+def test_bad_stamps_raise_before_launch():
+    K.check_stamp_errors()
+
+
+def test_custom_stamp_function_called_once_per_class():
+    K.check_custom_called_once()
+
+
+def test_as_tensor():
+    K.check_as_tensor()
+
+
+def test_crop_windows():
+    K.check_crop("cpu")
+
+
+@pytest.mark.parametrize("k", range(len(K.PATCH_SETTINGS)))
+def test_extract_patches_against_sklearn(k):
+    K.check_patches(k)
+
+
+def test_extract_random_subimages_against_reference():
+    K.check_random_subimages()
+
+
+def test_no_sklearn_scipy_cv2_behind_the_training_sets():
+    K.check_no_sklearn()
