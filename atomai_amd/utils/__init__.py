@@ -1,6 +1,8 @@
 from .coords import (cluster_coord, cluster_coord_frames, compare_coordinates, find_coord_clusters, gaussian_2d,
                      get_intensities, get_intensities_, get_nn_distances, get_nn_distances_, grid2xy, imcoordgrid,
                      map_bonds, peak_refinement, remove_edge_coord, transform_coordinates)
+from .graphx import (Graph, filter_subgraphs, filter_subgraphs_, find_cycle_clusters, find_cycles, find_cycles_frames,
+                     get_interatomic_r)
 from .imgen import (MakeAtom, create_atom_mask_pair, create_lattice_mask, create_multiclass_lattice_mask,
                     create_multiclass_lattice_mask_)
 from .img import (crop_borders, extract_patches, extract_patches_, extract_random_subimages, extract_subimages,

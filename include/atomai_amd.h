@@ -851,6 +851,40 @@ int amx_lattice_fill(const int* owner, const double* xy, const int* meta, long N
 int amx_crop_windows(const void* src, int esize, int is_float, int F, int H, int W, int C, const int* win, long P, int ph,
                      int pw, void* dst, int* flag, void* stream);
 
+/* ---- graph analysis of atom tables (atomai/utils/graphx.py: Graph.find_neighbors, polycount + remove_filled_polygons,
+ * and the networkx components behind find_cycle_clusters and filter_subgraphs), csrc/graph.hip.  One flat table of
+ * 0 <= N < 2^31 rows, S segments given by the int64 offsets seg [S+1] (the layout of amx_knn); rows of different
+ * segments never see one another.  fp64 and integers; no floating-point atomics; two runs give the same bits.
+ * A graph is a CSR: rowptr [N+1] int64 (rowptr[0] = 0, rowptr[N] = M), col [M] int32 = rows of the flat table, the
+ * neighbours of every row ascending; it must hold every bond from both ends.  Entries outside [0, N) are ignored.
+ * amx_bond_count: pts [N][3] fp64, cls [N] int32 in [0, C), 1 <= C <= 16, cut2 [C][C] fp64.  Rows i != j of one segment
+ *   are bonded if dx*dx + dy*dy + dz*dz <= cut2[cls[i]][cls[j]] in fp64, added in that order without contraction (false
+ *   for NaN; rows at the same position are bonded; a row whose class is outside [0, C) has no bonds).  tiles [T][2]
+ *   int64 as for amx_knn: (segment, first row) of every tile of at most 256 consecutive rows of one segment, one
+ *   workgroup each.  Writes deg [N] int64, the number of bonds of every row a tile covers (the caller zeroes the rest).
+ * amx_bond_emit: with rowptr = the exclusive prefix sum of deg and M its total, writes the neighbours of row i, in
+ *   ascending row order, to col [rowptr[i], rowptr[i] + deg[i]); nothing is written at or beyond M.
+ * amx_graph_hook: one hooking round of the connected components of a CSR; the contract of amx_cluster_hook.  pin, pout
+ *   [N] int32; pin is read only and must be flat (pin[pin[i]] == pin[i]), pout must equal pin on entry.  For every
+ *   edge with roots a < b: pout[b] = min(pout[b], a) and *changed |= 1 (integer atomicMin / atomicOr).  Start from
+ *   parent[i] = i and alternate with amx_cluster_jump until *changed stays 0: parent[i] is then the smallest row of
+ *   the component of i.
+ * amx_ring_count: 3 <= L <= 16.  count [N] int64 = the rings whose smallest row is i.  A ring is a simple cycle of 3 to L
+ *   rows such that for every two of them no path in the whole graph is shorter than the shorter way round the cycle;
+ *   each is counted once.  One thread per root row; the search order is fixed by the order of col.
+ * amx_ring_emit: with offs [N] = the exclusive prefix sum of count and R = its total, repeats the search and writes ring
+ *   s of root i (in search order) to slot offs[i] + s: ring [R][16] int32 = its rows ascending, -1 behind them, len [R]
+ *   int32 = their number; nothing is written at or beyond R. */
+int amx_bond_count(const double* pts, const int* cls, long N, const double* cut2, int C, const long* seg, int S,
+                   const long* tiles, long T, long* deg, void* stream);
+int amx_bond_emit(const double* pts, const int* cls, long N, const double* cut2, int C, const long* seg, int S,
+                  const long* tiles, long T, const long* rowptr, long M, int* col, void* stream);
+int amx_graph_hook(const long* rowptr, const int* col, long N, long M, const int* pin, int* pout, int* changed,
+                   void* stream);
+int amx_ring_count(const long* rowptr, const int* col, long N, long M, int L, long* count, void* stream);
+int amx_ring_emit(const long* rowptr, const int* col, long N, long M, int L, const long* offs, long R, int* ring, int* len,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
